@@ -11,7 +11,13 @@ does.  Chain state, dataset and records stay resident in HBM; host formatting of
 At the end of the timed region ranks all-gather their per-chain summaries over RCCL (the one-sigma
 selection input) and the selected chains' records -- the only collectives.
 
-At N = 1 the same line also carries (`--legs`, default both):
+A plain run does only that: set up, warm up, time the steps, write the outputs when `--dump-outputs DIR` is
+given, print the result line.  Everything else the benchmark measures or checks runs under `--full` alone:
+the CPU baselines (oracle at -O2 and -O0), the parity leg (the CPU oracle reruns some of the timed chains and
+every compared saved record must match bit for bit), the posterior statistics and the digest of the selected
+chains' records, and the extra workloads below.
+
+With `--full`, at N = 1 the same line also carries (`--legs`, default both):
   config2 -- the reference's own published workload (Report p.6 s5.1: g10s10, 100 chains x 2000
              mcmc_sample calls in 15-20 min): script.py:48-67 end to end through the drop-in launcher,
              Chains/chain_NN files written, beside the CPU oracle CLI running the same protocol, whose
@@ -22,7 +28,7 @@ At N = 1 the same line also carries (`--legs`, default both):
 
 1 chain-iteration = 1 sweep = body of mcmc.c:225-244.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -43,6 +49,8 @@ G10S10 = os.path.join(ROOT, "tests", "golden", "datasets", "g10s10.txt")
 C5_GOLDEN = os.path.join(ROOT, "tests", "golden", "config5.json")
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 CHAINS_SELECTED = 8    # choose_chains(8) as in Report Table 1 for g10s10
+DUMP_SEED = 20261019   # --dump-outputs: the fixed sample of the saved calls when an array is over its budget
+DUMP_BUDGET = {"selected_records_ab_pi": 44 << 20, "chain_cdl": 12 << 20}   # bytes as written; the rest is small
 
 
 def launch_ranks(n):
@@ -113,6 +121,39 @@ def measured_traffic(N, M, chains, sweeps_per_step):
     if best is None:
         return None, None, {}
     return best[2]["traffic_bytes_per_launch"], os.path.relpath(best[1], ROOT), best[2]
+
+
+def sample_calls(k, T, w, itemsize, budget):
+    """Indices of the saved calls a [k, T, w] array keeps so that it fits `budget` bytes at `itemsize` per value:
+    all T when they fit, else a fixed (DUMP_SEED) sorted sample -- the same from run to run and build to build."""
+    import numpy as np
+    keep = max(1, int(budget // max(1, k * w * itemsize)))
+    if keep >= T:
+        return np.arange(T)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(T, keep, replace=False))
+
+
+def dump_outputs(dirname, gathered, selected, sel_ab, sel_cdl, chain_cdl):
+    """--dump-outputs: what the timed path handed back in its last run, one DIR/<name>.npy each (float32 / float64,
+    under 64 MB in all): the gathered exp_data summaries [chains, 4], the selected chain ids, the selected chains'
+    saved records (a, b, pi as float32 -- int16 values, exact; c, d, loglik as float64) and every chain of this
+    rank's (c, d, loglik) per saved call.  Arrays over their budget keep a fixed seeded sample of the saved calls,
+    whose indices are written beside them."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+
+    def put(name, a, dtype):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    put("summaries", gathered, np.float64)
+    put("selected_chains", np.asarray(selected), np.float64)
+    idx = sample_calls(sel_ab.shape[0], sel_ab.shape[1], sel_ab.shape[2], 4, DUMP_BUDGET["selected_records_ab_pi"])
+    put("selected_records_ab_pi", sel_ab[:, idx], np.float32)
+    put("selected_records_cdl", sel_cdl[:, idx], np.float64)
+    put("selected_records_calls", idx, np.float64)
+    idx = sample_calls(chain_cdl.shape[0], chain_cdl.shape[1], 3, 8, DUMP_BUDGET["chain_cdl"])
+    put("chain_cdl", chain_cdl[:, idx], np.float64)
+    put("chain_cdl_calls", idx, np.float64)
 
 
 def _cpu_worker(args):
@@ -320,6 +361,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=20, help="untimed steps first (the clocks ramp over the first ~10 launches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what they computed "
+                    "(summaries, selection, the selected chains' records, every chain's c / d / loglik) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the CPU baselines, the parity leg "
+                    "against the CPU oracle, the selection's posterior statistics and the config2 / config5 legs "
+                    "(--no-cpu-baseline, --parity-chains, --legs narrow these); without it none of them runs")
     ap.add_argument("--total-chains", type=int, default=100, help="chains in the whole job, sharded contiguously over "
                     "the N GPUs (ragged shards: dist.shard); the metric's 100 at every N (strong scaling); 800 = config 4")
     ap.add_argument("--chains-per-gpu", type=int, default=0, help="weak scaling instead: this many chains per GPU "
@@ -359,6 +405,8 @@ def main():
     ap.add_argument("--legs", default="auto", help="extra workloads in the same line at N = 1 (ignored at N > 1): "
                     "comma-separated from config2, config5; none; auto = both unless --no-cpu-baseline or N > 1")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline alone
+        args.no_cpu_baseline, args.legs, args.parity_chains = True, "none", 0
     legs = set()
     if args.legs == "auto":
         if args.gpus == 1 and not args.no_cpu_baseline:
@@ -502,8 +550,8 @@ def main():
     tail_parts = {"summaries_ms": (t_summ - t_kernels) * 1e3, "gather_select_ms": (t_sel - t_summ) * 1e3,
                   "copy_gather_records_ms": (time.perf_counter() - t_fetch) * 1e3}
     sel_ab, sel_cdl = dev_ab.cpu().numpy(), dev_cd.cpu().numpy()   # (host copies for the statistics: untimed)
-    # posterior statistics of the selected chains (script.py:100-152), outside the timed region
-    ec, ed, corr = sd.selection_statistics(sel_ab, sel_cdl, ds.N, ds.M, CHAINS_SELECTED)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered, selected, sel_ab, sel_cdl, sess.fetch_cdl())
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -588,13 +636,16 @@ def main():
                    "note": "gather_select_ms: after the last kernel, the per-chain summaries (exp_data kernel), "
                            "their all-gather, the one-sigma selection, and the selected chains' records copied "
                            "device to device and all-gathered on the device (inside the timed region)"},
-        "selection": {"chains_selected": selected, "exp_c": ec, "exp_d": ed, "corr_mn": corr,
-                      "samples_per_chain": nrec,
-                      "records_sha256": hashlib.sha256(np.ascontiguousarray(sel_ab).tobytes() +
-                                                       np.ascontiguousarray(sel_cdl).tobytes()).hexdigest(),
-                      "note": "script.py:70-152 over every timed step's saved samples of the selected chains (the "
-                              "reference divides by 1000: exact means at --steps 20 x 50 calls = 1000 samples)"},
+        "selection": {"chains_selected": selected, "samples_per_chain": nrec},
     }
+    if args.full:   # posterior statistics of the selected chains (script.py:100-152), outside the timed region
+        ec, ed, corr = sd.selection_statistics(sel_ab, sel_cdl, ds.N, ds.M, CHAINS_SELECTED)
+        out["selection"].update({
+            "exp_c": ec, "exp_d": ed, "corr_mn": corr,
+            "records_sha256": hashlib.sha256(np.ascontiguousarray(sel_ab).tobytes() +
+                                             np.ascontiguousarray(sel_cdl).tobytes()).hexdigest(),
+            "note": "script.py:70-152 over every timed step's saved samples of the selected chains (the "
+                    "reference divides by 1000: exact means at --steps 20 x 50 calls = 1000 samples)"})
     # parity leg inputs (outside the timed region, rank 0): besides the selected chains, chains the selection
     # rejected -- the first and the last of this rank's shard that were not selected -- so the check does not
     # sample only the best-loglik chains the records under test chose

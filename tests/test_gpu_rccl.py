@@ -15,7 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--chains-per-gpu", "24",
+ARGS = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--chains-per-gpu", "24",
         "--calls-per-step", "20"]
 
 
@@ -67,7 +67,7 @@ def test_bench_two_ranks_on_one_gpu_equals_single_process():
     selection on every rank, the record gather from non-zero owners and the max-over-ranks timing all run.
     The selection, the gathered records and E[c] / E[d] / CORRMN must equal a single process running all
     48 chains (script.py:55-99), and both lines' parity legs must match the oracle."""
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--calls-per-step", "20"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--calls-per-step", "20"]
     single = _bench_line([sys.executable, "bench.py", "--gpus", "1", "--chains-per-gpu", "48"] + common)
     two = _bench_line([sys.executable, "bench.py", "--gpus", "2", "--chains-per-gpu", "24", "--device-of-rank", "0,0",
                        "--dist-backend", "gloo"] + common)
@@ -92,7 +92,8 @@ def test_bench_total_chains_ragged_three_ranks_equals_single_process():
     --total-chains 100 the chains are sharded contiguously and raggedly (dist.shard: 33/33/34 over three ranks,
     13/13/13/13/12/12/12/12 over eight).  Three gloo ranks on the one GPU must give the single-process 100-chain
     line bit for bit -- selection, gathered records, E[c], E[d], CORRMN -- and both lines say strong scaling."""
-    common = ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--calls-per-step", "20", "--total-chains", "100"]
+    common = ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--calls-per-step", "20",
+              "--total-chains", "100"]
     single = _bench_line([sys.executable, "bench.py", "--gpus", "1"] + common)
     three = _bench_line([sys.executable, "bench.py", "--gpus", "3", "--device-of-rank", "0,0,0", "--dist-backend",
                          "gloo"] + common)

@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(256, 600), (200, 800), (128, 1000)]
 VARIANTS = {"lds512": ["--block-threads", "512", "--columns", "lds"],
             "hbm1024": ["--block-threads", "1024", "--columns", "hbm"]}
-COMMON = ["--no-cpu-baseline", "--legs", "none", "--parity-chains", "2", "--parity-rejected", "0", "--parity-calls", "2",
-          "--steps", "5", "--warmup", "3", "--calls-per-step", "10", "--total-chains", "100"]
+COMMON = ["--full", "--no-cpu-baseline", "--legs", "none", "--parity-chains", "2", "--parity-rejected", "0",
+          "--parity-calls", "2", "--steps", "5", "--warmup", "3", "--calls-per-step", "10", "--total-chains", "100"]
 
 
 def main():

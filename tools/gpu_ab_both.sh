@@ -9,8 +9,8 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$1; REPS=$2; v=$3
 mkdir -p "$OUT"
 VL=seriation-in-paleontological-data-using-mcmc_amd/build/var/$v/libseriation.so
-C5="--no-cpu-baseline --legs none --sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup 10 --parity-chains 2 --parity-rejected 0 --parity-calls 4"
-C3="--no-cpu-baseline --legs none"
+C5="--full --no-cpu-baseline --legs none --sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup 10 --parity-chains 2 --parity-rejected 0 --parity-calls 4"
+C3="--full --no-cpu-baseline --legs none"
 show() { python3 -c "import json;b=json.load(open('$1'));print('$2', round(b['roofline']['kernel_ms'],3), round(b['value']), b['parity']['match'])"; }
 for rep in $(seq 1 $REPS); do
   timeout -k 10 200 python bench.py $C5 > "$OUT/c5_product_$rep.json" 2> "$OUT/c5_product_$rep.err" && show "$OUT/c5_product_$rep.json" "c5 product $rep" &&

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 V=seriation-in-paleontological-data-using-mcmc_amd/build/var
 timeout -k 10 600 python -u -m pytest tests/test_gpu_edge.py tests/test_gpu_config5.py -k "hbm or per-thread or tb1024 or n2500 or config5" -x -q --timeout 300 --timeout-method thread > "$OUT/parity.log" 2>&1 || { tail -30 "$OUT/parity.log"; exit 1; }
 tail -1 "$OUT/parity.log"
-C5="--sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup 3"
+C5="--full --sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup 3"
 for tb in 1024 512; do
   timeout -k 10 200 python bench.py --no-cpu-baseline $C5 --block-threads $tb > "$OUT/c5new_$tb.json" 2> "$OUT/c5new_$tb.err" || exit 1
   SERIATION_LIB=$V/$OLD/libseriation.so timeout -k 10 200 python bench.py --no-cpu-baseline $C5 --block-threads $tb > "$OUT/c5old_$tb.json" 2> "$OUT/c5old_$tb.err" || exit 1

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$1; REPS=$2; shift 2
 mkdir -p "$OUT"
 V=seriation-in-paleontological-data-using-mcmc_amd/build/var
-C5="--no-cpu-baseline --legs none --sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup ${WARM:-10} --parity-chains 2 --parity-rejected 0 --parity-calls 4"
+C5="--full --no-cpu-baseline --legs none --sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup ${WARM:-10} --parity-chains 2 --parity-rejected 0 --parity-calls 4"
 for rep in $(seq 1 $REPS); do
   timeout -k 10 200 python bench.py $C5 > "$OUT/product_$rep.json" 2> "$OUT/product_$rep.err" || exit 1
   echo "product $rep $(python3 -c "import json;b=json.load(open('$OUT/product_$rep.json'));print(round(b['roofline']['kernel_ms'],3), b['parity']['match'])")"

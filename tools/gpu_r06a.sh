@@ -16,6 +16,6 @@ tail -3 "$OUT/pytest_new.log"
 timeout -k 10 300 python tests/cert_run.py > "$OUT/cert_product.json" 2> "$OUT/cert.err" &&
 SERIATION_LIB=seriation-in-paleontological-data-using-mcmc_amd/build/cert8/libseriation.so \
   timeout -k 10 300 python tests/cert_run.py > "$OUT/cert_shift8.json" 2>> "$OUT/cert.err" || exit 1
-timeout -k 10 500 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 500 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 python3 tools/ab_planner.py "$OUT" || exit 1
 echo done

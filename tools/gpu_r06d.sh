@@ -15,8 +15,8 @@ mkdir -p "$OUT"
 timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { cat "$OUT/smoke.log"; exit 1; }
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 400 --timeout-method thread > "$OUT/pytest_gpu.log" 2>&1 || { tail -40 "$OUT/pytest_gpu.log"; exit 1; }
 tail -2 "$OUT/pytest_gpu.log"
-timeout -k 10 500 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
-Q="--legs none --no-cpu-baseline --parity-chains 2 --parity-rejected 0 --parity-calls 20"
+timeout -k 10 500 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+Q="--full --legs none --no-cpu-baseline --parity-chains 2 --parity-rejected 0 --parity-calls 20"
 for rep in 1 2; do
   for tb in 512 256; do
     timeout -k 10 200 python bench.py $Q --block-threads $tb > "$OUT/tb${tb}_$rep.json" 2> "$OUT/tb${tb}_$rep.err" || exit 1

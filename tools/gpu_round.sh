@@ -13,13 +13,13 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-round}
 mkdir -p "$OUT"
-B="bench.py"
-BT="bench.py --legs none --no-cpu-baseline"   # the headline's kernels alone (the legs run other shapes)
+B="bench.py --full"
+BT="bench.py --full --legs none --no-cpu-baseline"   # the headline's kernels alone (the legs run other shapes)
 P="bench.py --no-cpu-baseline --parity-chains 0 --steps 5 --warmup 3"
 C5="bench.py --no-cpu-baseline --parity-chains 0 --sites 1024 --taxa 2048 --calls-per-step 2 --steps 10 --warmup 3 --block-threads 1024"
 # the config-5 bench line re-checks its first 4 saved calls of 2 selected chains against the oracle (the CPU
 # oracle takes ~25 ms per 1024 x 2048 sweep); the profiled runs skip the parity leg
-C5B="${C5/--parity-chains 0/--parity-chains 2 --parity-calls 4}"
+C5B="${C5/--parity-chains 0/--full --parity-chains 2 --parity-calls 4}"
 SQA="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA"
 SQB="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_BRANCH"
 if [ "$2" != "skip-tests" ]; then
