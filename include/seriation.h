@@ -246,6 +246,40 @@ int sr_posterior(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int3
 int sr_session_posterior(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
                          int32_t chains_selected, sr_posterior_out *out);
 
+/* ---- convergence diagnostics over saved samples: split-R-hat and effective sample size ----
+ * (an extension: the reference has none).  Quantity q runs over the W = 2M+N integer columns of a record row
+ * (a | b | pi), then c, d, loglik (log scale as stored; manycd: taxon 0's): Q = W + 3.  Each of the n_sel chains'
+ * `count` (>= 4) records gives two sequences of h = count / 2 rows, rows [0, h) and [count - h, count); S = 2 n_sel
+ * sequences, chain 0's halves first.  Lags 0..L, L = max_lag (0 = h - 1; < 0 or >= h: SR_EINVAL).
+ * The GPU computes the exact int64 moments of every integer column x_t of every sequence,
+ *   P[s][k][j] = sum_{t <= h-1-k} x_t x_{t+k},  F[s][k][j] = sum_{t < k} x_t,  B[s][k][j] = sum_{t >= h-k} x_t,
+ *   S1[s][j] = sum_t x_t;
+ * the host forms G = h^2 P_k - h S1 (2 S1 - B_k - F_k) + (h - k) S1^2 exactly (128-bit), rounds it to f64 once,
+ * gamma_k = G / h^3 (biased autocovariance), m = S1 / h, var = gamma_0 h / (h - 1); the scalar columns take the
+ * same quantities from two sequential f64 passes.  Then, in f64 (sums over sequences in ascending order):
+ * Wv = mean var, Bh = sum (m - mean m)^2 / (S - 1), vp = (h-1)/h Wv + Bh, rhat = sqrt(vp / Wv),
+ * rho_k = 1 - (Wv - mean gamma_k) / vp, Geyer's initial monotone sequence over the pairs rho_2j + rho_2j+1
+ * (cut_lag = 2j of the first negative pair, -1 if the lags ran out: ess is then an upper estimate),
+ * tau = max(-1 + 2 sum, 1 / log10(S h)), ess = S h / tau: the split-R-hat / ESS of BDA3 and Vehtari et al. 2021
+ * without rank normalisation.  A column that never moved (Wv = 0) has rhat = ess = NaN, cut_lag = -1. */
+typedef struct {
+  int32_t max_lag;                 /* in: 0 = h-1 */
+  double *rhat, *ess;              /* [2M+N+3], NULL = skip */
+  int32_t *cut_lag;                /* [2M+N+3], NULL = skip */
+  int64_t *P, *F, *B, *S1;         /* optional raw moments: [S][L+1][W], [S][L+1][W], [S][L+1][W], [S][W]; NULL = skip */
+  double kernel_ms;                /* out */
+} sr_diag_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16, cdl [n_sel][count][3] (NULL: scalar entries NaN) */
+int sr_diagnostics(const sr_dataset *ds, const int16_t *ab_pi, const double *cdl, int32_t n_sel, int32_t count,
+                   int32_t device, sr_diag_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order) */
+int sr_session_diagnostics(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                           sr_diag_out *out);
+/* host only, no GPU: moments (+ optional scalar traces cdl [n_sel][count][3]) -> rhat / ess / cut_lag */
+int sr_diag_reduce(int32_t W, int32_t n_sel, int32_t count, int32_t max_lag, const int64_t *P, const int64_t *F,
+                   const int64_t *B, const int64_t *S1, const double *cdl, double *rhat, double *ess, int32_t *cut_lag);
+
 const char *sr_strerror(int code);
 int sr_device_count(void);
 const char *sr_version(void);

@@ -1077,6 +1077,251 @@ SR_API int sr_session_posterior(sr_session *s, const int32_t *chains, int32_t n_
   return post_rc(rc);
 }
 
+/* ---- convergence diagnostics: split-R-hat and ESS (definitions: include/seriation.h) ---- */
+/* The device layer's moment kernels (sr_diag.hip); absent from the host-only builds, whose device stubs
+   predate them: weak, so those builds link and sr_diagnostics reports SR_EUNSUPPORTED. */
+extern __typeof__(srd_moments_dev) srd_moments_dev __attribute__((weak));
+extern __typeof__(srd_moments_host) srd_moments_host __attribute__((weak));
+
+/* Running sums over the sequences, fed in ascending sequence order (so any number of sequences at a time). */
+typedef struct {
+  int W, Q, S, h, L, ns;        /* ns: integer sequences added so far */
+  double *gsum;                 /* [L+1][Q] sum over sequences of gamma_k */
+  double *mean, *var;           /* [S][Q] */
+} diag_acc;
+
+static void diag_free(diag_acc *a)
+{
+  free(a->gsum); free(a->mean); free(a->var);
+  a->gsum = a->mean = a->var = NULL;
+}
+
+static int diag_begin(diag_acc *a, int W, int n_sel, int count, int L)
+{
+  a->W = W; a->Q = W + 3; a->S = 2 * n_sel; a->h = count / 2; a->L = L; a->ns = 0;
+  a->gsum = (double *)calloc((size_t)(L + 1) * a->Q, sizeof(double));
+  a->mean = (double *)calloc((size_t)a->S * a->Q, sizeof(double));
+  a->var = (double *)calloc((size_t)a->S * a->Q, sizeof(double));
+  if (!a->gsum || !a->mean || !a->var) { diag_free(a); return SR_ENOMEM; }
+  return SR_OK;
+}
+
+/* the integer columns of the next n sequences: P, F, B [n][L+1][W], S1 [n][W] */
+static void diag_add_int(diag_acc *a, int n, const int64_t *P, const int64_t *F, const int64_t *B, const int64_t *S1)
+{
+  const int W = a->W, Q = a->Q, h = a->h, L = a->L;
+  const double h3 = (double)h * h * h;
+  for (int i = 0; i < n; i++, a->ns++) {
+    const int s = a->ns;
+    for (int k = 0; k <= L; k++) {
+      const size_t row = ((size_t)i * (L + 1) + k) * W;
+      for (int j = 0; j < W; j++) {
+        const __int128 s1 = S1[(size_t)i * W + j];
+        const __int128 G = (__int128)h * h * P[row + j] - (__int128)h * s1 * (2 * s1 - B[row + j] - F[row + j])
+                           + (__int128)(h - k) * s1 * s1;
+        const double g = (double)G / h3;
+        a->gsum[(size_t)k * Q + j] += g;
+        if (k == 0) {
+          a->mean[(size_t)s * Q + j] = (double)S1[(size_t)i * W + j] / h;
+          a->var[(size_t)s * Q + j] = g * h / (h - 1);
+        }
+      }
+    }
+  }
+}
+
+/* the three scalar columns of every sequence: cdl [n_sel][count][3]; two sequential passes per sequence */
+static void diag_add_scalars(diag_acc *a, const double *cdl, int count)
+{
+  const int Q = a->Q, h = a->h, L = a->L;
+  for (int s = 0; s < a->S; s++) {
+    const double *x0 = cdl + ((size_t)(s >> 1) * count + ((s & 1) ? count - h : 0)) * 3;
+    for (int v = 0; v < 3; v++) {
+      const double *x = x0 + v;   /* x_t = x[3 t] */
+      const int q = a->W + v;
+      double sum = 0.0;
+      for (int t = 0; t < h; t++) sum += x[3 * t];
+      const double m = sum / h;
+      for (int k = 0; k <= L; k++) {
+        double acc = 0.0;
+        for (int t = 0; t < h - k; t++) acc += (x[3 * t] - m) * (x[3 * (t + k)] - m);
+        const double g = acc / h;
+        a->gsum[(size_t)k * Q + q] += g;
+        if (k == 0) a->var[(size_t)s * Q + q] = g * h / (h - 1);
+      }
+      a->mean[(size_t)s * Q + q] = m;
+    }
+  }
+}
+
+/* the f64 tail of quantities [q0, q1) */
+static void diag_finish(const diag_acc *a, int q0, int q1, double *rhat, double *ess, int32_t *cut_lag)
+{
+  const int Q = a->Q, S = a->S, h = a->h, L = a->L;
+  for (int q = q0; q < q1; q++) {
+    double sv = 0.0, sm = 0.0;
+    for (int s = 0; s < S; s++) sv += a->var[(size_t)s * Q + q];
+    for (int s = 0; s < S; s++) sm += a->mean[(size_t)s * Q + q];
+    const double Wv = sv / S, mm = sm / S;
+    double sb = 0.0;
+    for (int s = 0; s < S; s++) {
+      const double dm = a->mean[(size_t)s * Q + q] - mm;
+      sb += dm * dm;
+    }
+    const double Bh = sb / (S - 1);
+    const double vp = ((double)(h - 1) / (double)h) * Wv + Bh;
+    double r = NAN, e = NAN;
+    int cut = -1;
+    if (Wv != 0.0 && isfinite(vp)) {   /* (a NaN Wv compares unequal to 0 and gives a NaN vp: caught by isfinite) */
+#define DIAG_RHO(k) (1.0 - (Wv - a->gsum[(size_t)(k) * Q + q] / S) / vp)
+      r = sqrt(vp / Wv);
+      double prev = 1.0 + (L >= 1 ? DIAG_RHO(1) : 0.0), sum = prev;
+      for (int j = 1; 2 * j + 1 <= L; j++) {
+        double gj = DIAG_RHO(2 * j) + DIAG_RHO(2 * j + 1);
+        if (gj < 0.0) { cut = 2 * j; break; }
+        if (prev < gj) gj = prev;
+        sum += gj;
+        prev = gj;
+      }
+#undef DIAG_RHO
+      double tau = -1.0 + 2.0 * sum;
+      const double tmin = 1.0 / log10((double)S * h);
+      if (!(tau >= tmin)) tau = tmin;
+      e = (double)S * h / tau;
+    }
+    if (rhat) rhat[q] = r;
+    if (ess) ess[q] = e;
+    if (cut_lag) cut_lag[q] = cut;
+  }
+}
+
+static void diag_nan(const diag_acc *a, int q0, int q1, double *rhat, double *ess, int32_t *cut_lag)
+{
+  (void)a;
+  for (int q = q0; q < q1; q++) {
+    if (rhat) rhat[q] = NAN;
+    if (ess) ess[q] = NAN;
+    if (cut_lag) cut_lag[q] = -1;
+  }
+}
+
+/* L of (count, max_lag), or -1 */
+static int diag_lags(int32_t count, int32_t max_lag)
+{
+  if (count < 4) return -1;
+  const int h = count / 2;
+  if (max_lag < 0 || max_lag >= h) return -1;
+  return max_lag == 0 ? h - 1 : max_lag;
+}
+
+SR_API int sr_diag_reduce(int32_t W, int32_t n_sel, int32_t count, int32_t max_lag, const int64_t *P, const int64_t *F,
+                          const int64_t *B, const int64_t *S1, const double *cdl, double *rhat, double *ess,
+                          int32_t *cut_lag)
+{
+  const int L = diag_lags(count, max_lag);
+  if (W < 1 || n_sel <= 0 || n_sel > INT32_MAX / 2 || L < 0 || !P || !F || !B || !S1) return SR_EINVAL;
+  diag_acc a;
+  int rc = diag_begin(&a, W, n_sel, count, L);
+  if (rc) return rc;
+  diag_add_int(&a, a.S, P, F, B, S1);
+  diag_finish(&a, 0, W, rhat, ess, cut_lag);
+  if (cdl) {
+    diag_add_scalars(&a, cdl, count);
+    diag_finish(&a, W, a.Q, rhat, ess, cut_lag);
+  } else {
+    diag_nan(&a, W, a.Q, rhat, ess, cut_lag);
+  }
+  diag_free(&a);
+  return SR_OK;
+}
+
+/* Both public forms: the moments of the chains in batches (bounded host and device buffers: the moments of 100
+   chains x 500 lags x 1280 columns are 3 GB), each batch reduced into the running sums.  rec = NULL: records in
+   host memory (ab_pi, chain k at k * count * W); else the device buffer rec with per-chain offsets off. */
+#define DIAG_BATCH_BYTES (256u << 20)
+static int diag_run(int W, int n_sel, int count, int L, const int16_t *ab_pi, int device, void *stream,
+                    const int16_t *rec, const long long *off, long long row_stride, const double *cdl, sr_diag_out *out)
+{
+  if (!srd_moments_dev || !srd_moments_host) return SR_EUNSUPPORTED;
+  const size_t lw = (size_t)(L + 1) * W, per_chain = 2 * lw * 3 * sizeof(int64_t);
+  int nb = (int)(DIAG_BATCH_BYTES / per_chain);
+  if (nb < 1) nb = 1;
+  if (nb > n_sel) nb = n_sel;
+  if (nb > 16384) nb = 16384;   /* one grid row per sequence */
+  diag_acc a;
+  int rc = diag_begin(&a, W, n_sel, count, L);
+  if (rc) return rc;
+  /* moments the caller did not ask for live in per-batch scratch */
+  int64_t *tP = out->P ? NULL : (int64_t *)malloc(2 * nb * lw * sizeof(int64_t));
+  int64_t *tF = out->F ? NULL : (int64_t *)malloc(2 * nb * lw * sizeof(int64_t));
+  int64_t *tB = out->B ? NULL : (int64_t *)malloc(2 * nb * lw * sizeof(int64_t));
+  int64_t *tS = out->S1 ? NULL : (int64_t *)malloc(2 * nb * (size_t)W * sizeof(int64_t));
+  if ((!out->P && !tP) || (!out->F && !tF) || (!out->B && !tB) || (!out->S1 && !tS)) rc = SR_ENOMEM;
+  out->kernel_ms = 0.0;
+  for (int c0 = 0; c0 < n_sel && !rc; c0 += nb) {
+    const int n = n_sel - c0 < nb ? n_sel - c0 : nb;
+    int64_t *bP = out->P ? out->P + 2 * c0 * lw : tP, *bF = out->F ? out->F + 2 * c0 * lw : tF;
+    int64_t *bB = out->B ? out->B + 2 * c0 * lw : tB, *bS = out->S1 ? out->S1 + 2 * (size_t)c0 * W : tS;
+    float ms = 0.0f;
+    int drc = rec ? srd_moments_dev(device, stream, rec, off + c0, n, count, row_stride, W, L, (long long *)bP,
+                                    (long long *)bF, (long long *)bB, (long long *)bS, &ms)
+                  : srd_moments_host(device, ab_pi + (size_t)c0 * count * W, n, count, W, L, (long long *)bP,
+                                     (long long *)bF, (long long *)bB, (long long *)bS, &ms);
+    if (drc) { rc = post_rc(drc); break; }
+    out->kernel_ms += ms;
+    diag_add_int(&a, 2 * n, bP, bF, bB, bS);
+  }
+  if (!rc) {
+    diag_finish(&a, 0, W, out->rhat, out->ess, out->cut_lag);
+    if (cdl) {
+      diag_add_scalars(&a, cdl, count);
+      diag_finish(&a, W, a.Q, out->rhat, out->ess, out->cut_lag);
+    } else {
+      diag_nan(&a, W, a.Q, out->rhat, out->ess, out->cut_lag);
+    }
+  }
+  free(tP); free(tF); free(tB); free(tS);
+  diag_free(&a);
+  return rc;
+}
+
+SR_API int sr_diagnostics(const sr_dataset *ds, const int16_t *ab_pi, const double *cdl, int32_t n_sel, int32_t count,
+                          int32_t device, sr_diag_out *out)
+{
+  if (!ds || !ab_pi || !out || n_sel <= 0 || n_sel > INT32_MAX / 2 || ds->N < 1 || ds->M < 1) return SR_EINVAL;
+  const int L = diag_lags(count, out->max_lag);
+  if (L < 0) return SR_EINVAL;
+  return diag_run(2 * ds->M + ds->N, n_sel, count, L, ab_pi, device, NULL, NULL, NULL, 0, cdl, out);
+}
+
+SR_API int sr_session_diagnostics(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                  sr_diag_out *out)
+{
+  if (!s || !chains || !out || n_sel <= 0 || n_sel > INT32_MAX / 2 || first < 0 || count < 0 || first + count > s->nrec)
+    return SR_EINVAL;
+  for (int k = 0; k < n_sel; k++)
+    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  const int L = diag_lags(count, out->max_lag);
+  if (L < 0) return SR_EINVAL;
+  if (!srd_moments_dev) return SR_EUNSUPPORTED;
+  const int16_t *rec;
+  int cap, dev;
+  void *stream;
+  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
+  const int W = 2 * s->ds.M + s->ds.N;
+  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
+  double *cdl = (double *)malloc(sizeof(double) * 3 * (size_t)n_sel * count);   /* the scalar columns: to the host */
+  int rc = (off && cdl) ? SR_OK : SR_ENOMEM;
+  for (int k = 0; k < n_sel && !rc; k++) {
+    off[k] = ((long long)chains[k] * cap + first) * W;
+    if (srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, cdl + (size_t)k * count * 3)) rc = SR_EDEVICE;
+  }
+  if (!rc) rc = diag_run(W, n_sel, count, L, NULL, dev, stream, rec, off, W, cdl, out);
+  free(off);
+  free(cdl);
+  return rc;
+}
+
 SR_API void sr_session_destroy(sr_session *s)
 {
   if (!s) return;

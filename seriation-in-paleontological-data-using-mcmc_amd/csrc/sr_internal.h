@@ -120,6 +120,15 @@ int srp_posterior_dev(int device, void *stream, int kind, const int16_t *d_rec, 
                       double *out_host, float *ms);
 int srp_posterior_host(int device, int kind, const int16_t *ab_pi, int n_sel, int count, int N, int M,
                        const uint8_t *X_host, int chains_selected, double *out_host, float *ms);
+/* convergence diagnostics (sr_diag.hip): the exact integer moments of n_sel chains' records, two sequences of
+   h = count / 2 rows per chain (rows [0, h) and [count - h, count)), lags 0..L (1 <= L < h): host buffers
+   P, F, B [2 n_sel][L+1][W] and S1 [2 n_sel][W], W = 2M + N.  sr_host.c refers to both weakly: the host-only
+   builds (device layer stubbed) have neither, and sr_diagnostics returns SR_EUNSUPPORTED there. */
+int srd_moments_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
+                    long long row_stride, int W, int L, long long *P, long long *F, long long *B, long long *S1,
+                    float *ms);
+int srd_moments_host(int device, const int16_t *ab_pi, int n_sel, int count, int W, int L, long long *P, long long *F,
+                     long long *B, long long *S1, float *ms);
 void srk_destroy(srk_dev *d);
 
 #ifdef __cplusplus

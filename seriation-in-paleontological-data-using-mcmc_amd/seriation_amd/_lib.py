@@ -73,6 +73,15 @@ class sr_posterior_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_diag_out(ctypes.Structure):
+    _fields_ = [("max_lag", ctypes.c_int32),
+                ("rhat", ctypes.POINTER(ctypes.c_double)), ("ess", ctypes.POINTER(ctypes.c_double)),
+                ("cut_lag", ctypes.POINTER(ctypes.c_int32)),
+                ("P", ctypes.POINTER(ctypes.c_int64)), ("F", ctypes.POINTER(ctypes.c_int64)),
+                ("B", ctypes.POINTER(ctypes.c_int64)), ("S1", ctypes.POINTER(ctypes.c_int64)),
+                ("kernel_ms", ctypes.c_double)]
+
+
 SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                            ctypes.POINTER(sr_record))
 
@@ -87,7 +96,8 @@ PUBLIC_SYMBOLS = [
     "sr_session_state",
     "sr_session_accept_counts", "sr_session_fallback_counts", "sr_session_debug_flagged", "sr_session_last_kernel_ms", "sr_session_block_threads", "sr_session_variant", "sr_session_specialized",
     "sr_session_checkpoint", "sr_session_restore",
-    "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior", "sr_strerror", "sr_device_count", "sr_version",
+    "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior",
+    "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_strerror", "sr_device_count", "sr_version",
 ]
 
 _LIB = None
@@ -146,6 +156,10 @@ def _lib():
         "sr_specialize": (c_int, [P(sr_dataset), P(sr_run_opts)]),
         "sr_posterior": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, c_i32, P(sr_posterior_out)]),
         "sr_session_posterior": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, c_i32, P(sr_posterior_out)]),
+        "sr_diagnostics": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, P(sr_diag_out)]),
+        "sr_session_diagnostics": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_diag_out)]),
+        "sr_diag_reduce": (c_int, [c_i32, c_i32, c_i32, c_i32, P(ctypes.c_int64), P(ctypes.c_int64), P(ctypes.c_int64),
+                                   P(ctypes.c_int64), P(c_double), P(c_double), P(c_double), P(c_i32)]),
         "sr_strerror": (ctypes.c_char_p, [c_int]),
         "sr_device_count": (c_int, []),
         "sr_version": (ctypes.c_char_p, []),

@@ -149,6 +149,101 @@ def session_records(session):
     return L.lib().sr_session_records(session.h)
 
 
+# ---------------------------------------------------------------- convergence diagnostics
+# Split-R-hat and effective sample size per site position, taxon limit, c, d and loglik (definitions:
+# include/seriation.h).  The lagged integer moments of the records come from the GPU (csrc/sr_diag.hip), exact in
+# int64; the f64 tail is the library's host code.  There is no CPU fallback for the moments.
+_I64P = ctypes.POINTER(ctypes.c_int64)
+_DBLP = ctypes.POINTER(ctypes.c_double)
+
+
+def _diag_lags(count, max_lag):
+    h = count // 2
+    return h, (h - 1 if max_lag == 0 else max_lag)
+
+
+def _diag_views(flat, N, M):
+    return {"a": flat[:M], "b": flat[M:2 * M], "pi": flat[2 * M:2 * M + N],
+            "c": flat[2 * M + N], "d": flat[2 * M + N + 1], "loglik": flat[2 * M + N + 2]}
+
+
+def _diag_outs(N, M, n_sel, count, max_lag, moments):
+    Q = 2 * M + N + 3
+    flat = {"rhat": np.zeros(Q), "ess": np.zeros(Q), "cut_lag": np.zeros(Q, np.int32)}
+    out = L.sr_diag_out()
+    out.max_lag = int(max_lag)
+    out.rhat = flat["rhat"].ctypes.data_as(_DBLP)
+    out.ess = flat["ess"].ctypes.data_as(_DBLP)
+    out.cut_lag = flat["cut_lag"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    raw = {}
+    # (invalid count / max_lag: no moment buffers; the library refuses the call with SR_EINVAL)
+    if moments and count >= 4 and 0 <= max_lag < count // 2 and n_sel > 0:
+        h, lags = _diag_lags(count, max_lag)
+        W, S = 2 * M + N, 2 * n_sel
+        raw = {"P": np.zeros((S, lags + 1, W), np.int64), "F": np.zeros((S, lags + 1, W), np.int64),
+               "B": np.zeros((S, lags + 1, W), np.int64), "S1": np.zeros((S, W), np.int64)}
+        for k, a in raw.items():
+            setattr(out, k, a.ctypes.data_as(_I64P))
+    return out, flat, raw
+
+
+def _diag_result(out, flat, raw, N, M):
+    res = {k: _diag_views(v, N, M) for k, v in flat.items()}
+    res["kernel_ms"] = out.kernel_ms
+    res.update(raw)
+    return res
+
+
+def diagnostics_from_records(dataset, ab_pi, cdl=None, max_lag=0, device=0, moments=False):
+    """sr_diagnostics: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order), cdl
+    [n_sel][count][3] (c, d, loglik; None: their entries are NaN) -> {"rhat", "ess", "cut_lag": {"a": [M], "b": [M],
+    "pi": [N], "c", "d", "loglik"}, "kernel_ms"}; moments=True adds the raw int64 moments "P", "F", "B"
+    [2 n_sel][L+1][2M+N] and "S1" [2 n_sel][2M+N]."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    cd = None
+    if cdl is not None:
+        cd = np.ascontiguousarray(cdl, dtype=np.float64)
+        assert cd.shape == (n_sel, count, 3)
+    out, flat, raw = _diag_outs(dataset.N, dataset.M, n_sel, count, max_lag, moments)
+    _check(L.lib().sr_diagnostics(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)),
+                                  cd.ctypes.data_as(_DBLP) if cd is not None else None, n_sel, count, device,
+                                  ctypes.byref(out)), "sr_diagnostics")
+    return _diag_result(out, flat, raw, dataset.N, dataset.M)
+
+
+def diagnostics_from_session(session, chains, first=0, count=None, max_lag=0, moments=False):
+    """sr_session_diagnostics: the same over a session's records still in HBM, rows [first, first + count) of
+    chains (session chain indices in selection order)."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, flat, raw = _diag_outs(session.ds.N, session.ds.M, len(chains), count, max_lag, moments)
+    _check(L.lib().sr_session_diagnostics(session.h, ch, len(chains), first, count, ctypes.byref(out)),
+           "sr_session_diagnostics")
+    return _diag_result(out, flat, raw, session.ds.N, session.ds.M)
+
+
+def diag_reduce(P, F, B, S1, count, max_lag=0, cdl=None):
+    """sr_diag_reduce (host only, no GPU): moments P, F, B [S][L+1][W], S1 [S][W] of S = 2 n_sel sequences of
+    count // 2 rows (+ optional scalar traces cdl [n_sel][count][3]) -> (rhat, ess, cut_lag), each [W + 3]."""
+    P, F, B, S1 = (np.ascontiguousarray(x, dtype=np.int64) for x in (P, F, B, S1))
+    S, W = S1.shape
+    h, lags = _diag_lags(count, max_lag)
+    assert S % 2 == 0 and P.shape == F.shape == B.shape == (S, lags + 1, W)
+    cd = None
+    if cdl is not None:
+        cd = np.ascontiguousarray(cdl, dtype=np.float64)
+        assert cd.shape == (S // 2, count, 3)
+    rhat, ess, cut = np.zeros(W + 3), np.zeros(W + 3), np.zeros(W + 3, np.int32)
+    _check(L.lib().sr_diag_reduce(W, S // 2, count, int(max_lag), P.ctypes.data_as(_I64P), F.ctypes.data_as(_I64P),
+                                  B.ctypes.data_as(_I64P), S1.ctypes.data_as(_I64P),
+                                  cd.ctypes.data_as(_DBLP) if cd is not None else None, rhat.ctypes.data_as(_DBLP),
+                                  ess.ctypes.data_as(_DBLP), cut.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+           "sr_diag_reduce")
+    return rhat, ess, cut
+
+
 def read_chain_rows(root, chains, sites, taxa):
     """chain_data.csv of each chain -> int16 [n][lines][2M+N] (fields 0, 1, 2 tokens as the script
     slices them).  All chains must hold the same number of lines."""
