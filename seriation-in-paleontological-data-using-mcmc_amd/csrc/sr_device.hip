@@ -295,7 +295,7 @@ __host__ __device__ static inline size_t sr_sp_ck(int N, int TB) { return (size_
 #define MS_BLK 7
 #define MS_OFF 8
 #define MS_GEN 9
-#define MS_LOGL 10
+#define MS_LOGL 10     /* (free: mcmc_logl is no longer broadcast) */
 #define MS_CAB 11
 #define MS_LLS 12
 #define MS_NEXACT 13
@@ -1463,11 +1463,19 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
         t[g] = *reinterpret_cast<const double2 *>(T8 + 2 * e);
       }
     };
+    /* Walk words that can hold a whole walk byte: the walk has at most N + 1 entries, (N + 1) >> 3 whole bytes,
+       4 to a word.  With the shape compiled in, a word past them (word 8 at N <= 262: it holds whole bytes from
+       L = 263) has only dead entries for every L, and a dead step leaves S and y bit for bit as they are
+       (fma(y, 0, S), y * 1; a y that is not finite still reaches S through the partial-byte step below): no
+       reads and no Horner step for it.  The 9-word kernels only (the 17-word ones: not measured). */
+    constexpr int NWC = (((SR_FN + 1) >> 3) + 3) >> 2;
+    constexpr int NWB = (SR_FN > 0 && NWM <= 9 && NWC < NWM) ? NWC : NWM;
     double2 t[4], tn[4];
     wload(0, t);
 #pragma unroll
     for (int k = 0; k < NWM; ++k) {
-      if (k + 1 < NWM) wload(k + 1, tn);   /* next word's reads in flight while this word is summed */
+      if (k >= NWB) { yst[k] = y; ckr[k] = S; continue; }
+      if (k + 1 < NWB) wload(k + 1, tn);   /* next word's reads in flight while this word is summed */
       yst[k] = y;
       {   /* the word's 4 byte steps in Horner form: one multiply on the y chain per word */
         const double w23 = __builtin_fma(t[2].y, t[3].x, t[2].x);
@@ -1980,6 +1988,68 @@ __device__ __forceinline__ double exact_sum_gm(const double *cbuf, const int *cc
   return s;
 }
 
+/* mcmc_logl's sum (mcmc.c:639-645) over the terms in LDS, by one lane: strictly left to right in m, one
+ * rounding per term (s = s + lbuf[m]).  Whole blocks of 16 terms are read (8 x ds_read_b128: lbuf is 16-byte
+ * aligned, sr_layout) into two register blocks used in turn, the next block's reads issued before this block's
+ * 16 dependent adds, so the add chain does not wait for LDS (the form this replaces read 4 terms, waited, added
+ * 4: 41-47 cycles per term against 4-8 for a dependent v_add_f64).  The scheduling barriers keep that order:
+ * without them the compiler sinks the reads to the top of the next trip, in front of the adds that need them.
+ * The tail (M mod 16 terms) is read first, under everything else, and added last; its reads are clamped to the
+ * last aligned pair, which lies inside lbuf's slot (padded to 16 bytes), and only the terms m < M are added. */
+#define SR_LOGL_D 16   /* terms per block */
+__device__ __forceinline__ void logl_block_load(const double *p, double2 (&t)[SR_LOGL_D / 2])
+{
+#pragma unroll
+  for (int q = 0; q < SR_LOGL_D / 2; ++q) t[q] = *reinterpret_cast<const double2 *>(p + 2 * q);
+}
+__device__ __forceinline__ double logl_block_add(double s, const double2 (&t)[SR_LOGL_D / 2])
+{
+#pragma unroll
+  for (int q = 0; q < SR_LOGL_D / 2; ++q) { s = s + t[q].x; s = s + t[q].y; }
+  return s;
+}
+__device__ __forceinline__ double logl_sum_lds(const double *lbuf, int M)
+{
+  constexpr int D = SR_LOGL_D;
+  const int nb = M / D, mt = nb * D;   /* whole blocks; the tail's first term */
+  const int ML = (M - 1) & ~1;         /* the last aligned pair */
+  const bool tail = mt < M;
+  double2 ta[D / 2], tb[D / 2], tc[D / 2];
+  if (tail) {
+#pragma unroll
+    for (int q = 0; q < D / 2; ++q) tc[q] = *reinterpret_cast<const double2 *>(lbuf + min(mt + 2 * q, ML));
+  }
+  double s = 0.0;
+  int b = 0;
+  if (nb > 0) logl_block_load(lbuf, ta);
+  for (; b + 3 <= nb; b += 2) {   /* ta holds block b; two blocks per trip: they swap roles without copies */
+    logl_block_load(lbuf + (b + 1) * D, tb);
+    __builtin_amdgcn_sched_barrier(0);
+    s = logl_block_add(s, ta);
+    __builtin_amdgcn_sched_barrier(0);
+    logl_block_load(lbuf + (b + 2) * D, ta);
+    __builtin_amdgcn_sched_barrier(0);
+    s = logl_block_add(s, tb);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (nb - b == 2) {
+    logl_block_load(lbuf + (b + 1) * D, tb);
+    __builtin_amdgcn_sched_barrier(0);
+    s = logl_block_add(s, ta);
+    s = logl_block_add(s, tb);
+  } else if (nb - b == 1) {
+    s = logl_block_add(s, ta);
+  }
+  if (tail) {   /* exactly the terms mt <= m < M, in order */
+#pragma unroll
+    for (int q = 0; q < D / 2; ++q) {
+      if (mt + 2 * q < M) s = s + tc[q].x;
+      if (mt + 2 * q + 1 < M) s = s + tc[q].y;
+    }
+  }
+  return s;
+}
+
 /* ---------------------------------------------------------------- proposals */
 #define PK_PI1 1
 #define PK_PI2 20
@@ -2449,7 +2519,10 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   double d = A.cdl[(size_t)chain * 4 + 1];
   double *cv = MCD ? A.cdv + (size_t)chain * 2 * M : nullptr;   /* manycd: c[M], d[M] (HBM state, updated in place) */
   double *cx = MCD ? A.cdx + (size_t)chain * 2 * M : nullptr;   /* manycd: log(1 - e^c[m]), log(1 - e^d[m]) */
-  double loglik = A.cdl[(size_t)chain * 4 + 2];   /* identical in every thread */
+  /* meaningful in thread 0 only, its one reader (the saved record, the stored state): the one-workgroup LDS-column
+     kernels sum mcmc_logl there alone; every thread adds the accepted moves' deltas (block-uniform).  The HBM-column
+     kernels still hold the same value in every thread. */
+  double loglik = A.cdl[(size_t)chain * 4 + 2];
   DRng R;
   R.ring = ring;
   {
@@ -2645,6 +2718,16 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       STAMP(5);
 #endif
       FST(0);
+      /* The 8-wave one-workgroup LDS-column kernels put two waves on each SIMD, and VALU issue goes to the older wave
+         first: at equal priority waves 4-7 take 30 % longer over the same branch-free Gibbs draws (26.8 k against
+         20.7 k cycles per sweep, profiles/r07a_stampbar_perwave_parent_warm500.log) and every barrier waits for them.
+         They run phase B at priority 1, and both halves reach phase C's batch barrier together (-5.1 % per launch).
+         For phase B only: raised for the whole kernel it is slower than no priority at all (+1.5 %), and kept up to
+         the batch barrier +3.9 % against this form (profiles/r07b_ab_prio_readlane.json, r07c_ab_final.json).
+         (s_setprio ignores EXEC: the condition is a scalar.) */
+      if constexpr (!GM && !PR && TB == 512) {
+        if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= TB / 2) __builtin_amdgcn_s_setprio(1);
+      }
       /* ============ phase B: Gibbs update of own (a_m, b_m) (mcmc_sampleab) */
       /* taxa in rounds of TB (round r: m = r*TB + tid, words 2(m - r*TB), +1 from the round's
          cursor), each round's 2*TB words made resident first: the ring holds < 2M words when
@@ -2762,6 +2845,9 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
         const int nw = wave_sum_i32((int)nchg);
         if (lane == 0 && nw) atomicAdd((unsigned long long *)&misc[MS_CAB], (unsigned long long)nw);
       }
+      if constexpr (!GM && !PR && TB == 512) {   /* ... and back */
+        if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= TB / 2) __builtin_amdgcn_s_setprio(0);
+      }
       FST(1);
       STAMP(1);
       if (GM && want_logl) {   /* mcmc_logl with the terms in HBM: each wave reads them 64 at a time
@@ -2784,26 +2870,14 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           }
         }
         loglik = s;
-      } else if (want_logl) {   /* mcmc_logl (mcmc.c:639-645), sequential over m, lane 0 of every wave */
-        SR_SYNC();
-        if (PR ? tid == 0 : lane == 0) {
-          double s = 0.0;
-          int m = 0;
-          for (; m + 4 <= M; m += 4) {
-            const double a0 = lbuf[m], a1 = lbuf[m + 1], a2 = lbuf[m + 2], a3 = lbuf[m + 3];
-            s = s + a0; s = s + a1; s = s + a2; s = s + a3;
-          }
-          for (; m < M; ++m) s = s + lbuf[m];
-          if (PR) *reinterpret_cast<double *>(&misc[MS_LOGL]) = s; else *xs = s;
-        }
-        if constexpr (PR) {   /* one sum (thread 0), read by all behind a barrier */
-          SR_SYNC();
-          loglik = *reinterpret_cast<const double *>(&misc[MS_LOGL]);
-        } else {
-          wsync();
-          loglik = *xs;
-          wsync();
-        }
+      } else if (want_logl) {   /* mcmc_logl (mcmc.c:639-645), sequential over m, by thread 0 alone */
+        SR_SYNC();   /* every wave's terms are in lbuf */
+        /* Only thread 0 reads loglik (the saved record, the stored state), so only it sums; the other waves go
+           straight on to phase C and nothing is broadcast.  lbuf is not written again before thread 0 is done
+           with it: its only writer is the Gibbs step of a later logl sweep, which every wave reaches through
+           this sweep's end-of-sweep barrier at the earliest, and wave 0 arrives there after its sum.  No other
+           array shares lbuf's slot (sr_layout). */
+        if (tid == 0) loglik = logl_sum_lds(lbuf, M);
       }
       STAMP(2);
       FST(0);

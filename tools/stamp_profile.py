@@ -2,6 +2,9 @@
 """Phase breakdown of the sweep kernel from an SR_STAMPS build (diagnostic only).
 
   SERIATION_LIB=<pkg>/build/stamps/libseriation.so python tools/stamp_profile.py [dataset] [chains] [calls]
+
+Environment: SR_WARM=n (calls before the profiled launch), SR_BAR=1 (SR_STAMP_BAR builds: barrier waits),
+SR_WAVES=1 (every wave's row for each phase, and its barrier wait with SR_BAR=1).
 """
 import ctypes
 import os
@@ -67,6 +70,13 @@ if os.environ.get("SR_BAR") and nw <= 8:   # SR_STAMPS + SR_STAMP_BAR builds: cy
     tot = per[:, :, :8].sum(2)
     print("  barrier wait (cycles/sweep): wave0 %.0f, mean wave %.0f = %.1f %% of the mean wave's sweep" % (
         bar[:, 0].mean(), bar.mean(), 100.0 * bar.mean() / tot.mean()))
+if os.environ.get("SR_WAVES"):   # every wave's row (chain mean): which waves are the slow ones, and where they wait
+    print("  per wave (cycles/sweep, chain mean)" + "".join("%9s" % ("w%d" % w) for w in range(nw)))
+    for k, name in enumerate(PH):
+        print("  %-35s" % name + "".join("%9.0f" % per[:, w, k].mean() for w in range(nw)))
+    print("  %-35s" % "total" + "".join("%9.0f" % per[:, w, :].sum(1).mean() for w in range(nw)))
+    if os.environ.get("SR_BAR") and nw <= 8:
+        print("  %-35s" % "barrier wait (inside the rows)" + "".join("%9.0f" % bar[:, w].mean() for w in range(nw)))
 if os.environ.get("SR_GIBBS_STATS"):
     h = out[:, 0, :].astype(np.float64).sum(0)
     nd = max(h[4], 1)
