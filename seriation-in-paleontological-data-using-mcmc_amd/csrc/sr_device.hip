@@ -73,34 +73,18 @@ struct KArgs {
   unsigned long long *dbg;   /* SR_STAMPS builds: [chain][16] cycles per phase */
   uint16_t *gpre;            /* gm variant scratch, per chain: column prefix tables */
   uint32_t *pkey;            /* [chain][2] Philox keys (SR_F_RNG_PHILOX), else null: MT19937 */
-  void *gck;                     /* gm variant scratch: Gibbs checkpoints (SR_CK32: f32, half the bytes of the scratch stream;
-                                    unused by the split kernels, whose checkpoints are in LDS: SR_SP_LCK) */
+  double *gck;                   /* gm variant scratch: Gibbs checkpoints */
   double *glbuf, *gcbuf;         /* gm variant scratch: logl terms, exact-delta terms */
   int *xflag, *xbuf, *xerr;      /* split chains (SP kernels): [chain][2] progress flags, exchange slots, timeout flag */
   double *cdv, *cdx;   /* manycd (MCD kernels): [chain][2M] per-taxon c, d (state); [chain][2M] their cc, dd (scratch) */
   double *rec_cdv;     /* manycd: [chain][rec_cap][2M] per-taxon c, d of every saved sample */
 };
 
-/* The launch arguments re-read from the kernarg segment (constant for the launch; the kernel's only
- * argument is KArgs, at offset 0): the record and state pointers used after the sweeps come from here, so
- * they are not held live (in spilled SGPRs) across the sweep loop.  SR_KARG_RELOAD=0: the by-value copy. */
-/* HBM-column kernels: Gibbs checkpoints stored as f32 (1) or f64 (0) in their HBM scratch (draw_fast).
-   f32 halves the scratch stream but is rejected (r04c/r04d, same box): the certification's absolute slack
-   must then grow to 2^-21 S, and an entry with less mass than twice the slack can never be certified, so
-   u landing in the window's many small-mass entries sends ~1.3e-4 of the draws to the exact walk (0.52
-   per chain-sweep against 0.0025 in f64): config 5 ran 2.3x slower (10.45 vs 4.56 ms per launch). */
-#ifndef SR_CK32
-#define SR_CK32 0
-#endif
 /* HBM-column kernels: window words per stored Gibbs checkpoint (pass 2 re-sums the chosen group's words in
    one round trip; 4 measured fastest: 4.56 / 4.44 / 4.39 ms per config-5 launch at 1 / 2 / 4, r04e-r04f) */
 #ifndef SR_CKG
 #define SR_CKG 4
 #endif
-/* split-chain kernels (SP): the Gibbs checkpoints in LDS ((N/32)/SR_CKG + 1 slots per thread) instead of HBM
-   scratch, room made by one block-shared copy of the hard-site and 4-step tables instead of one per wave
-   (16 waves: 66 KB + 20 KB at N = 1024).  The checkpoints were a quarter of config 5's HBM traffic (all of its
-   writes) and two dependent memory round trips of every walk's pass 2 (0 = HBM scratch, round 4's form) */
 /* test builds: every certification margin -- the Gibbs picks' REL / ABS (draw_fast, walk_pick_s, draw_pair9) and
    phase C's Eb (pc_classify) -- scaled by 2^-SR_CERT_SHIFT.  The product is 0; the negative control of
    tests/test_gpu_cert.py builds the library at 8 and must then see wrong picks and decisions, which shows that the
@@ -109,35 +93,20 @@ struct KArgs {
 #define SR_CERT_SHIFT 0
 #endif
 #define SR_CERT_SCALE (1.0 / (double)(1ull << SR_CERT_SHIFT))
-#ifndef SR_SP_LCK
-#define SR_SP_LCK 1
-#endif
-/* split kernels whose LDS layout has room (LK): the own half's column prefix table in LDS (stride = the half's
-   taxa) and the Gibbs checkpoints in HBM scratch, instead of the checkpoints in LDS and the prefixes in HBM: the
-   prefixes are read several times per proposal and taxon, the checkpoints once per walk, and the L2 holds the
-   columns of 25 half-chains per XCD (config 5: 4.208 -> 4.151 ms per launch, profiles/r06u_ab_c5_lpre.json) */
-#ifndef SR_SP_LPRE
-#define SR_SP_LPRE 1
-#endif
-/* HBM-column kernels: one block-shared copy of the hard-site and 4-step tables (16 waves at 1024 threads held 64 N
-   bytes of per-wave hard tables: at N ~ 1250 the layout passed 160 KB; shared, N reaches 4095 at 1024 threads) */
-#ifndef SR_GM_SHARED
-#define SR_GM_SHARED 1
-#endif
-/* the sweep's proposal tables filled by all threads before the phase-A barrier, and the swap drawn from them
-   (round 5; 0 = each wave fills its own at the start of phase C and the swap takes the scalar path) */
-#ifndef SR_COOP_TABLES
-#define SR_COOP_TABLES 1
-#endif
-/* the register form of an accepted pi1 in the HBM-column kernels too (off: in round 5 its registers spilled 37 more
-   VGPRs there, r05l) */
-#ifndef SR_GM_APPLY_REG
-#define SR_GM_APPLY_REG 0
-#endif
+/* The launch arguments as the code after the sweep loop reads them (the record and state pointers).  An identity: the
+   call is kept because without it the compiler places the address arithmetic of the kernel's state load differently,
+   and the removal of this file's experiment switches was held to identical instructions ("Retired
+   experiments"); the next tuning pass with a GPU at hand can drop it. */
+__device__ __forceinline__ const KArgs &kargs_late(const KArgs &A) { return A; }
 /* the proposal sums of a batch of at least this many proposals by one transposed reduction per wave
    (wave_sum32_t; 0 = one reduction per slot) */
 #ifndef SR_TSUMS
 #define SR_TSUMS 4
+#endif
+/* at most this many proposals per batch (a smaller batch wastes fewer evaluations after an accepted proposal,
+   at the cost of more batches) */
+#ifndef SR_BATCH_MAX
+#define SR_BATCH_MAX 16
 #endif
 /* diagnostic builds (tools/build_variant.sh): SR_DOUBLE = k does phase k's work twice, the second result folded
    in through an opaque zero (the chain is unchanged), so the time difference is the phase's marginal cost:
@@ -151,60 +120,6 @@ __device__ __forceinline__ int sr_opaque_zero()
   int z;
   __asm__ volatile("s_mov_b32 %0, 0" : "=s"(z));
   return z;
-}
-/* the swap drawn into one batch with proposals 1..15 (its acceptance, ~44 %, then wastes their terms) */
-#ifndef SR_MERGE_SWAP
-#define SR_MERGE_SWAP 1
-#endif
-#ifndef SR_MERGE_SWAP_GM   /* ... also in the HBM-column kernels (their proposal terms cost far more) */
-#define SR_MERGE_SWAP_GM 0
-#endif
-/* the c, d draws' ziggurat steps read before the phase-A barrier (measured +0.5 %: off, r05q) */
-#ifndef SR_CD_PREFETCH
-#define SR_CD_PREFETCH 0
-#endif
-/* pi1's taxon change by one unsigned compare per limit */
-#ifndef SR_PI1_FAST
-#define SR_PI1_FAST 1
-#endif
-/* the per-lane "owns a taxon" test as a constant in shape-specialised kernels whose taxa fill the block */
-#ifndef SR_OWN_CONST
-#define SR_OWN_CONST 1
-#endif
-/* at most this many proposals per batch (a smaller batch wastes fewer evaluations after an accepted proposal,
-   at the cost of more batches) */
-#ifndef SR_BATCH_MAX
-#define SR_BATCH_MAX 16
-#endif
-/* ininterval as one unsigned range compare per lane */
-#ifndef SR_ININT_FAST
-#define SR_ININT_FAST 1
-#endif
-/* an accepted pi1 applied from registers: the taxon's words, moved bit and prefix read before any write */
-#ifndef SR_APPLY_REG
-#define SR_APPLY_REG 1
-#endif
-/* the main batch's proposal slots without per-slot branches (one-taxon kernels) */
-#ifndef SR_FULL_BATCH
-#define SR_FULL_BATCH 0
-#endif
-/* branch-free proposal terms (taxon_dt: no exec-mask branches, indices clamped, results selected) */
-#ifndef SR_BF_TERMS
-#define SR_BF_TERMS 0
-#endif
-#ifndef SR_KARG_RELOAD
-#define SR_KARG_RELOAD 0
-#endif
-__device__ __forceinline__ const KArgs &kargs_late(const KArgs &A)
-{
-#if SR_KARG_RELOAD
-  (void)A;
-  const KArgs *p = (const KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
-  __asm__ volatile("" : "+s"(p));   /* an opaque pointer: the loads stay here, after the loop */
-  return *p;
-#else
-  return A;
-#endif
 }
 
 /* ---------------------------------------------------------------- LDS carve */
@@ -230,19 +145,19 @@ __host__ __device__ static constexpr inline int sr_ckstride(int M, int TB) { ret
  * owner-thread access, L2/MALL-resident) and get no LDS slot */
 /* taxa per exact-delta chunk (one wave's taxa): 64, or 32 in the pair kernels (two lanes per taxon) */
 __host__ __device__ static constexpr inline int sr_chunk(bool pr) { return pr ? 32 : 64; }
-/* gm (SR_GM_SHARED): shared hard-site and 4-step tables; lck (split-chain kernels, SR_SP_LCK): Gibbs checkpoints in LDS */
-__host__ __device__ static constexpr inline int sr_lck_slots(int N) { return (N >> 5) / SR_CKG + 1; }
+/* gm: one block-shared copy of the hard-site and 4-step tables (a copy per wave passed 160 KB at N ~ 1250 and 1024
+ * threads; shared, N reaches 4095); lpre (split-chain kernels whose layout has room): the own half's column prefix
+ * table in LDS (stride = the half's taxa) instead of HBM scratch */
 __host__ __device__ static constexpr inline Lay sr_layout(int N, int M, int NW, int TB, bool gm, bool pr = false, int nh = 0,
-                                                          bool lck = false)
+                                                          bool lpre = false)
 {
   Lay L{};
   size_t o = 0;
   const int CH = sr_chunk(pr), KT = (M + CH - 1) / CH, NWV = TB / 64;
   const size_t g = gm ? 0 : 1;
-  lck = lck && gm;
-  const bool sht = gm && SR_GM_SHARED;
+  lpre = lpre && gm;
   /* step tables: one copy per wave, or one shared copy behind a barrier (pair kernels: 16 waves) */
-  const size_t NT = (pr || sht) ? 1 : NWV;
+  const size_t NT = (pr || gm) ? 1 : NWV;
   L.tab = o;   o = sr_al16(o + 512 * sizeof(double));   /* glibc exp/log tables */
   L.cbuf = o;  o = sr_al16(o + g * 2 * KT * CH * sizeof(double));       /* [2][KT*CH] by proposal parity */
   L.lbuf = o;  o = sr_al16(o + g * M * sizeof(double));
@@ -250,10 +165,9 @@ __host__ __device__ static constexpr inline Lay sr_layout(int N, int M, int NW, 
   L.P = o;     o = sr_al16(o + g * NW * M * 4);
   L.rpi0 = o;  o = sr_al16(o + (size_t)N * 4);
   L.rpi1 = o;  o = sr_al16(o + (size_t)N * 4);
-  L.ht = o;    o = sr_al16(o + (sht ? 1 : (size_t)NWV) * (2 * N + 2) * 2);   /* per wave (gm: shared): hcnt[N+1], nhall[N] (int16) */
+  L.ht = o;    o = sr_al16(o + (gm ? 1 : (size_t)NWV) * (2 * N + 2) * 2);   /* per wave (gm: shared): hcnt[N+1], nhall[N] (int16) */
   const size_t rw = (pr || sr_regwalk(N, M, TB, gm, nh)) ? 1 : 0;   /* register walks (pair kernels too): byte tables instead of LDS checkpoints */
-  L.ck = o;    o = sr_al16(o + g * (1 - rw) * ((N >> 5) + 1) * sr_ckstride(M, TB) * sizeof(double) +
-                           ((lck && !SR_SP_LPRE) ? (size_t)sr_lck_slots(N) * TB * sizeof(double) : 0));
+  L.ck = o;    o = sr_al16(o + g * (1 - rw) * ((N >> 5) + 1) * sr_ckstride(M, TB) * sizeof(double));
   L.ccnt = o;  o = sr_al16(o + (size_t)2 * KT * 4);
   L.sab = o;   o = sr_al16(o + g * 2 * M * 4);
   L.scnt = o;  o = sr_al16(o + g * 4 * M * 4);
@@ -261,9 +175,8 @@ __host__ __device__ static constexpr inline Lay sr_layout(int N, int M, int NW, 
   L.hbw = o;   o = sr_al16(o + (size_t)NWV * NW * 4);                 /* per wave: hard bitmap */
   L.t4 = o;    o = sr_al16(o + NT * 160 * 8);                         /* per wave: 4-entry step tables (T4STRIDE) */
   L.t8 = o;    o = sr_al16(o + (rw ? NT : (gm ? 1 : 0)) * T8STRIDE * 8);   /* per wave (gm: one shared copy): 8-entry step tables */
-  /* column prefix ones per word boundary (SR_SP_LPRE split kernels: the own half's, (((M + 1) / 2 + 63) & ~63) taxa =
-     sr_sp_half) */
-  L.pre = o;   o = sr_al16(o + (g * M + ((lck && SR_SP_LPRE) ? (size_t)((((M + 1) / 2) + 63) & ~63) : 0)) * (NW + 1) * 2);
+  /* column prefix ones per word boundary (lpre: the own half's, (((M + 1) / 2 + 63) & ~63) taxa = sr_sp_half) */
+  L.pre = o;   o = sr_al16(o + (g * M + (lpre ? (size_t)((((M + 1) / 2) + 63) & ~63) : 0)) * (NW + 1) * 2);
   L.part = o;  o = sr_al16(o + (size_t)2 * 16 * NWV * 8 * 4);         /* [2][proposal][wave] count sums */
   L.tot = o;   o = sr_al16(o + (size_t)2 * NWV * 4 * 4);               /* [2][wave] t0, f0, t1, f1 */
   L.xs = o;    o = sr_al16(o + (size_t)NWV * sizeof(double));          /* per-wave broadcast slot */
@@ -646,8 +559,7 @@ __device__ __forceinline__ double readlane_f64(double v, int l)
  * and the caller runs the sequential draws from the same cursor.  Wave-level: every wave of the
  * block computes it identically (no block synchronisation). */
 /* The part of draw_cd_fast that does not depend on the counts: lane g (& 3)'s two words from the cursor and its
- * ziggurat step (x, and whether the word falls inside the box), read before the phase-A barrier so that the table
- * lookups (global constant memory) overlap the wait.  ok = false: the words are not resident (no prefetch). */
+ * ziggurat step (x, and whether the word falls inside the box).  ok = false: the words are not resident. */
 struct CDPre { uint32_t w1; double x; bool box, ok; };
 __device__ __forceinline__ CDPre cd_prefetch(const DRng &r, int lane)
 {
@@ -672,14 +584,14 @@ __device__ __forceinline__ CDPre cd_prefetch(const DRng &r, int lane)
 }
 
 __device__ __forceinline__ bool draw_cd_fast(DRng &r, double &c, double &d, int f1, int t0, int f0, int t1,
-                                             const sr_mtab &tb, int lane, CDPre pf = CDPre{})
+                                             const sr_mtab &tb, int lane)
 {
 #ifdef SR_FORCE_EXACT   /* test build: the sequential GSL draws */
   return false;
 #endif
   if (r.blk + (r.off + 7) / SR_MT_N >= r.gen) return false;
   if ((f1 == 0 && t0 == 0) || (f0 == 0 && t1 == 0)) return false;   /* a Johnk beta: the sequential path */
-  if (!pf.ok) pf = cd_prefetch(r, lane);
+  const CDPre pf = cd_prefetch(r, lane);
   const int g = lane & 3;
   const uint32_t w1 = pf.w1;
   const int cnt = (g == 0) ? f1 : (g == 1) ? t0 : (g == 2) ? f0 : t1;
@@ -838,15 +750,6 @@ __device__ __forceinline__ int col_pre(const uint16_t *prem, const uint32_t *Pm,
   return (int)prem[w * (PS ? PS : M)] + __popc(word & ((1u << bits) - 1u));   /* PS: the table's own stride */
 }
 
-/* the same without a branch: the word read always (row 0 when x is a multiple of 32, masked to nothing),
-   so a proposal's taxon terms carry no exec-mask branches and the slots' reads can be in flight together */
-__device__ __forceinline__ int col_pre_bf(const uint16_t *prem, const uint32_t *Pm, int M, int x, int PS = 0)
-{
-  const int w = x >> 5, bits = x & 31;
-  const uint32_t word = Pm[(bits ? w : 0) * M];
-  return (int)prem[w * (PS ? PS : M)] + __popc(word & ((1u << bits) - 1u));
-}
-
 /* 32 walk bits [32k, 32k+32): fwd = positions, rev = positions N-1-w (bit i = walk 32k+i) */
 __device__ __forceinline__ uint32_t walk_word(const uint32_t *Pm, int M, int N, int NW, bool rev, int k)
 {
@@ -944,9 +847,7 @@ __device__ __forceinline__ double exp2_split(double q)
 template <bool B8>
 __device__ __forceinline__ int draw_fast(const uint32_t *Pm, const uint16_t *prem, int M, int N, int NW, bool rev, int o, int L,
                                          int POo, double u, const CD &K, const sr_mtab &tb, double vA, double vB, double rA, double rB,
-                                         const double *T4, const double *T8,
-                                         typename std::conditional<B8 && SR_CK32, float, double>::type *ck,
-                                         int ckstride, int PS, uint64_t *fbk, int &dt0, int &df0,
+                                         const double *T4, const double *T8, double *ck, int ckstride, int PS, uint64_t *fbk, int &dt0, int &df0,
                                          int &dt1, int &df1 GSTAMP_ARGS)
 {
   /* POo: ones among walk entries [0, o), from the caller's column prefix table */
@@ -1089,17 +990,12 @@ __device__ __forceinline__ int draw_fast(const uint32_t *Pm, const uint16_t *pre
      sum by at most ~9 2^-53 S (the subtraction and the word's fma roundings in pass 1): the extra
      absolute slack 2^-46 in u covers it; the unscaled sums' own rounding (and, with the byte tables in
      pass 1, the relative difference of the two table forms, <= 2 x 16 ulp) is inside REL's + 32.
-     B8 with SR_CK32 (HBM columns, not the default): the checkpoints are stored as f32: each is within
-     2^-24 S of its f64 value, so the word search may land one word off (then the word's first or last
-     entry fails its certification and the exact walk runs) and a reconstructed partial sum moves by at
-     most 3 2^-24 S (Sp0, Sj and y = (Sj - Sp0) / sum): the absolute slack grows by 2^-21 -- and every
-     entry with less mass than that slack fails certification, which measured 200x more exact walks.
      Ones before the word from the column prefix table. */
   int res = -1, POp = 0;
   if (S > 0.0 && S < 0x1p1000 && !uf) {
     const double inv = 1.0 / S;
     const double REL = (double)(N + 33) * 0x1p-50 * SR_CERT_SCALE;
-    const double ABS = ((double)(N + 1) * 0x1p-39 + 0x1p-46 + ((B8 && SR_CK32) ? 0x1p-21 : 0.0)) * SR_CERT_SCALE;
+    const double ABS = ((double)(N + 1) * 0x1p-39 + 0x1p-46) * SR_CERT_SCALE;
     int j = klo;   /* first window word whose checkpoint reaches u (checkpoints ascend) */
     double Sp0, yj;   /* the partial sum before word j, y at its start */
     if (B8 && SR_CKG > 1) {
@@ -1112,12 +1008,12 @@ __device__ __forceinline__ int draw_fast(const uint32_t *Pm, const uint16_t *pre
       for (int k0 = 0; k0 < ngrp - 1; k0 += SR_WCH) {
         double cv[SR_WCH];
 #pragma unroll
-        for (int t = 0; t < SR_WCH; ++t) cv[t] = (k0 + t < ngrp - 1) ? (double)ck[(k0 + t) * ckstride] : 0.0;
+        for (int t = 0; t < SR_WCH; ++t) cv[t] = (k0 + t < ngrp - 1) ? ck[(k0 + t) * ckstride] : 0.0;
 #pragma unroll
         for (int t = 0; t < SR_WCH; ++t) g += (k0 + t < ngrp - 1 && cv[t] * inv < u) ? 1 : 0;
       }
-      const double Sa = (g == 0) ? 0.0 : (double)ck[(g - 1) * ckstride];
-      const double Sb = (g == ngrp - 1) ? S : (double)ck[g * ckstride];
+      const double Sa = (g == 0) ? 0.0 : ck[(g - 1) * ckstride];
+      const double Sb = (g == ngrp - 1) ? S : ck[g * ckstride];
       const int k1 = klo + SR_CKG * g;
       uint32_t gw[SR_CKG];
 #pragma unroll
@@ -1166,12 +1062,12 @@ __device__ __forceinline__ int draw_fast(const uint32_t *Pm, const uint16_t *pre
       for (int k0 = klo; k0 < khi; k0 += SR_WCH) {
         double cv[SR_WCH];
 #pragma unroll
-        for (int t = 0; t < SR_WCH; ++t) cv[t] = (k0 + t < khi) ? (double)ck[(k0 + t) * ckstride] : 0.0;
+        for (int t = 0; t < SR_WCH; ++t) cv[t] = (k0 + t < khi) ? ck[(k0 + t) * ckstride] : 0.0;
 #pragma unroll
         for (int t = 0; t < SR_WCH; ++t) j += (k0 + t < khi && cv[t] * inv < u) ? 1 : 0;
       }
-      Sp0 = (j == klo) ? 0.0 : (double)ck[(j - 1) * ckstride];
-      yj = (j == khi) ? S : (double)ck[j * ckstride];   /* (Sj: y follows from it below) */
+      Sp0 = (j == klo) ? 0.0 : ck[(j - 1) * ckstride];
+      yj = (j == khi) ? S : ck[j * ckstride];   /* (Sj: y follows from it below) */
     }
     int Oj;   /* ones among walk entries [0, 32 j) */
     if (!rev) Oj = (int)prem[j * (PS ? PS : M)];
@@ -1826,17 +1722,9 @@ __device__ __forceinline__ int ininterval(int i, int a, int b, int inc1, int inc
   /* i inside the interval of ends a, b (ordered first; inc1 / inc2 include the lower / upper end): for integers
      that is L <= i <= H with L = lo + !inc1, H = hi - !inc2, one unsigned compare per lane (the ends and flags
      are block-uniform: scalar ALU) */
-#if SR_ININT_FAST
   const int lo = min(a, b), hi = max(a, b);
   const int L = lo + (inc1 ? 0 : 1), H = hi - (inc2 ? 0 : 1);
   return (H >= L) && (uint32_t)(i - L) <= (uint32_t)(H - L);
-#else
-  int r;
-  if (a > b) { r = a; a = b; b = r; }
-  r = inc1 ? (a <= i) : (a < i);
-  if (r) r = inc2 ? (i <= b) : (i < b);
-  return r;
-#endif
 }
 
 /* hard-site positions hp[0..nh) are ascending (their relative order never changes) */
@@ -2180,7 +2068,7 @@ __device__ __forceinline__ HM hard_bits_col(const uint32_t *Pm, int M, int hl, i
 template <typename HM>
 __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, const uint32_t *Pm, const uint16_t *prem,
                                          int M, HM hbm, const int16_t *hcnt, const int16_t *nhall, int &dt0, int &dt1,
-                                         const uint32_t *hbx, int N_, int PS = 0)
+                                         const uint32_t *hbx, int PS = 0)
 {
   const int i = q.i, j = q.j;
   dt0 = 0; dt1 = 0;
@@ -2188,37 +2076,16 @@ __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, 
     const int ii = q.ii, jj = q.jj;
     const int v = (Pm[(i >> 5) * M] >> (i & 31)) & 1;
     int sgn = 0;   /* +1: the moved site enters the taxon's range, -1: leaves it */
-#if SR_PI1_FAST
     {   /* i < j: a, b tested against [ii + 1, jj + 1], sgn = ain - bin; i > j: against [ii, jj], sgn = bin - ain
            (block-uniform bounds: one unsigned compare per limit) */
       const int up = i < j ? 1 : 0, L = ii + up, span = jj - ii;
       const int ain = (uint32_t)(a - L) <= (uint32_t)span, bin = (uint32_t)(b - L) <= (uint32_t)span;
       sgn = up ? ain - bin : bin - ain;
     }
-#else
-    if (i < j) {
-      const bool ain = (ii < a && a <= jj + 1), bin = (ii < b && b <= jj + 1);
-      sgn = (ain && !bin) ? 1 : ((!ain && bin) ? -1 : 0);
-    } else {
-      const bool ain = (ii <= a && a <= jj), bin = (ii <= b && b <= jj);
-      sgn = (!ain && bin) ? 1 : ((ain && !bin) ? -1 : 0);
-    }
-#endif
     if (v) dt1 = sgn; else dt0 = -sgn;
   } else if (kind != PK_PI3) {
     const int ain = ininterval(a, i, j + 1, q.inc1, q.inc2);
     const int bin = ininterval(b, i, j + 1, q.inc1, q.inc2);
-#if SR_BF_TERMS
-    {   /* branch-free: every lane reads the three prefixes, lanes with ain == bin keep zeros */
-      const int sp = ain ? a : b;
-      const int c0 = col_pre_bf(prem, Pm, M, i, PS), c1 = col_pre_bf(prem, Pm, M, sp, PS), c2 = col_pre_bf(prem, Pm, M, j + 1, PS);
-      const int O1 = c1 - c0, O2 = c2 - c1;
-      const int Z1 = (sp - i) - O1, Z2 = (j + 1 - sp) - O2;
-      const bool on = ain != bin;
-      dt1 = on ? (ain ? O1 - O2 : O2 - O1) : 0;
-      dt0 = on ? (ain ? Z2 - Z1 : Z1 - Z2) : 0;
-    }
-#else
     if (ain != bin) {
       const int sp = ain ? a : b;
       const int c0 = col_pre(prem, Pm, M, i, PS), c1 = col_pre(prem, Pm, M, sp, PS), c2 = col_pre(prem, Pm, M, j + 1, PS);
@@ -2227,7 +2094,6 @@ __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, 
       if (ain) { dt1 = O1 - O2; dt0 = Z2 - Z1; }
       else { dt1 = O2 - O1; dt0 = Z1 - Z2; }
     }
-#endif
   } else {
     const int ain = ininterval(a, i, j + 1, q.inc1, q.inc2);
     const int bin = ininterval(b, i, j + 1, q.inc1, q.inc2);
@@ -2244,16 +2110,6 @@ __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, 
     const int ri = q.r0;                                   /* = i - hcnt[i] */
     const int s_lo = (xa - hcnt[xa]) - ri, s_hi = (xb - hcnt[xb]) - ri;
     auto hard_ones = [&](int lo, int hi, int &cnt) -> int {   /* hard positions in [lo, hi] */
-#if SR_BF_TERMS
-      if (!hbx) {   /* branch-free: indices clamped into the tables, an empty range counts nothing */
-        const bool e = hi < lo;
-        const int kl = hcnt[min(max(lo, 0), N_)], kh = hcnt[min(max(hi + 1, 0), N_)];
-        cnt = e ? 0 : kh - kl;
-        constexpr int HB = 8 * (int)sizeof(HM);
-        const HM km = ((kh >= HB) ? ~(HM)0 : (((HM)1 << kh) - (HM)1)) & ~((kl >= HB) ? ~(HM)0 : (((HM)1 << kl) - (HM)1));
-        return e ? 0 : (int)__popcll((uint64_t)(hbm & km));
-      }
-#endif
       if (hi < lo) { cnt = 0; return 0; }
       const int kl = hcnt[lo], kh = hcnt[hi + 1];
       cnt = kh - kl;
@@ -2269,19 +2125,6 @@ __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, 
     const int wlo = max(a, i), whi = min(b - 1, j);
     const int sizeW = max(0, whi - wlo + 1);
     int onesI = 0, sizeI = 0;
-#if SR_BF_TERMS
-    const int onesW = (whi >= wlo) ? col_pre_bf(prem, Pm, M, max(whi + 1, 0), PS) - col_pre_bf(prem, Pm, M, wlo, PS) : 0;
-    {   /* branch-free: nhall indices and the positions read clamped into range, an empty rank range adds 0 */
-      const bool on = s_lo < s_hi;
-      const int pl = min(max((int)nhall[min(max(ri + q.Kn - s_hi, 0), N_ - 1)], 0), N_ - 1);
-      const int ph = min(max((int)nhall[min(max(ri + q.Kn - s_lo - 1, 0), N_ - 1)], 0), N_ - 1);
-      int hc;
-      const int ho = hard_ones(pl, ph, hc);
-      const int oI = col_pre_bf(prem, Pm, M, ph + 1, PS) - col_pre_bf(prem, Pm, M, pl, PS) - ho;
-      onesI = on ? oI : 0;
-      sizeI = on ? s_hi - s_lo : 0;
-    }
-#else
     const int onesW = (whi >= wlo) ? col_pre(prem, Pm, M, whi + 1, PS) - col_pre(prem, Pm, M, wlo, PS) : 0;
     if (s_lo < s_hi) {
       const int pl = nhall[ri + q.Kn - s_hi], ph = nhall[ri + q.Kn - s_lo - 1];
@@ -2290,7 +2133,6 @@ __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, 
       onesI = col_pre(prem, Pm, M, ph + 1, PS) - col_pre(prem, Pm, M, pl, PS) - ho;
       sizeI = s_hi - s_lo;
     }
-#endif
     {
       int hc;
       const int ho = hard_ones(max(na, i), min(nb - 1, j), hc);
@@ -2328,7 +2170,7 @@ __device__ __forceinline__ double sr_exact_delta(int kind, Prop q, CD K, const i
     int dt0 = 0, dt1 = 0;
     if (m < M && ev)
       taxon_dt(kind, q, sab[m], sab[M + m], P + m, pre + m, M, kind == PK_PI3 ? hard_bits_col<uint64_t>(P + m, M, hl, nh) : 0ull,
-               hcnt, nhall, dt0, dt1, hbx, N, PS);
+               hcnt, nhall, dt0, dt1, hbx, PS);
     CD Km = K;
     if (kv && m < M) { Km.c = kv[m]; Km.d = kv[M + m]; Km.cc = kx[m]; Km.dd = kx[M + m]; }
     const double tv = (m < M && ev) ? qval(dt0, -dt0, dt1, -dt1, Km) : 0.0;
@@ -2404,11 +2246,12 @@ __device__ __forceinline__ bool pc_resolve(double S, double Eb, int c0, int kz, 
   return false;
 }
 
-template <int TB, int NWM, bool GM, bool PR = false, bool SP = false, bool MCD = false, bool LK = false>
+template <int TB, int NWM, bool GM, bool PR = false, bool SP = false, bool MCD = false, bool LPRE = false>
 __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
 {
   static_assert(!SP || (GM && !PR && NWM == 0), "split chains: HBM-column kernels only");
   static_assert(!MCD || (!PR && !SP && NWM == 0), "manycd: generic one-workgroup kernels only");
+  static_assert(!LPRE || SP, "column prefixes in LDS beside HBM columns: split chains only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NWV = TB / 64;
   /* wave: scalar in the HBM-column kernels (readfirstlane), so their per-wave LDS pointers live in SGPRs */
@@ -2428,11 +2271,10 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   const int olo = SP ? half * sr_sp_half(M) : 0, ohi = SP ? min(M, olo + sr_sp_half(M)) : M;   /* own taxa */
   const int mt = olo + tx;   /* own taxon, one-taxon-per-thread kernels */
   const int KTC = (M + sr_chunk(PR) - 1) / sr_chunk(PR);   /* exact-delta chunks */
-  constexpr bool LCK = SP && LK && !SR_SP_LPRE;   /* Gibbs checkpoints in LDS (split kernels whose layout fits them, SR_SP_LCK) */
-  constexpr bool LPRE = SP && LK && SR_SP_LPRE;   /* ... or the own half's column prefixes in LDS instead (SR_SP_LPRE) */
+  /* LPRE (split kernels whose LDS layout has room): the own half's column prefix table in LDS instead of HBM scratch
+     -- the prefixes are read several times per proposal and taxon (config 5: 4.208 -> 4.151 ms per launch) */
   const int PS = LPRE ? sr_sp_half(M) : M;          /* the prefix table's stride */
-  constexpr bool SHT = GM && SR_GM_SHARED;   /* block-shared hard-site / 4-step tables */
-  const Lay L = sr_layout(N, M, NW, TB, GM, PR, nh, SP && LK);
+  const Lay L = sr_layout(N, M, NW, TB, GM, PR, nh, LPRE);
   double *tabs = (double *)(smem + L.tab);
   /* GM: the per-taxon arrays are the chain's HBM state itself (P, a/b, counts: updated in
      place) or its HBM scratch; otherwise LDS copies loaded here and stored at the end */
@@ -2444,11 +2286,10 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   int32_t *rpiB = (int32_t *)(smem + L.rpi1);
   uint16_t *pre = LPRE ? (uint16_t *)(smem + L.pre) - olo   /* (own taxa [olo, ohi) only) */
                  : GM ? A.gpre + (size_t)chain * sr_gm_pre(M, NW) : (uint16_t *)(smem + L.pre);   /* column prefix ones */
-  int16_t *hcnt = (int16_t *)(smem + L.ht) + (SHT ? 0 : wave) * (2 * N + 2);    /* this wave's (SHT: the block's) hard-site tables */
+  int16_t *hcnt = (int16_t *)(smem + L.ht) + (GM ? 0 : wave) * (2 * N + 2);    /* this wave's (GM: the block's) hard-site tables */
   int16_t *nhall = hcnt + N + 1;
-  const int CKS = LCK ? TB : SP ? 2 * TB : sr_ckstride(M, TB);   /* SP: slots [half TB + tid] (LCK: [tid] in LDS) */
-  using CKT = typename std::conditional<GM && SR_CK32, float, double>::type;   /* Gibbs checkpoints: f32 in HBM scratch, f64 in LDS */
-  CKT *ckb = (GM && !LCK) ? (CKT *)A.gck + (size_t)chain * (SP ? sr_sp_ck(N, TB) : sr_gm_ck(N, M, TB)) : (CKT *)(void *)(smem + L.ck);
+  const int CKS = SP ? 2 * TB : sr_ckstride(M, TB);   /* SP: slots [half TB + tid] */
+  double *ckb = GM ? A.gck + (size_t)chain * (SP ? sr_sp_ck(N, TB) : sr_gm_ck(N, M, TB)) : (double *)(smem + L.ck);   /* Gibbs checkpoints */
   int *ccnt = (int *)(smem + L.ccnt);
   int32_t *sab = GM ? A.ab + (size_t)chain * 2 * M : (int32_t *)(smem + L.sab);     /* a[M], b[M] */
   int32_t *scnt = GM ? A.cnt + (size_t)chain * 4 * M : (int32_t *)(smem + L.scnt);  /* t0[M], f0[M], t1[M], f1[M] */
@@ -2456,7 +2297,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   int *hp = (int *)(smem + L.hpw) + wave * NHC;   /* this wave's copy of the hard positions */
   uint32_t *hbw = (uint32_t *)(smem + L.hbw) + wave * NW;   /* this wave's hard bitmap */
   const uint32_t *hbx = nh > SR_NHMAX ? hbw : nullptr;   /* many hard sites: hard ones from the bitmap */
-  double *T4w = (double *)(smem + L.t4) + ((PR || SHT) ? 0 : wave) * T4STRIDE;   /* this wave's (PR, SHT: the block's) 4-step tables */
+  double *T4w = (double *)(smem + L.t4) + ((PR || GM) ? 0 : wave) * T4STRIDE;   /* this wave's (PR, GM: the block's) 4-step tables */
   constexpr bool SH8 = PR || GM;   /* one shared copy of the 8-step tables (built by waves 0-3, then a barrier) */
   double *T8w = (double *)(smem + L.t8) + (SH8 ? 0 : wave) * T8STRIDE;   /* this wave's (SH8: the block's) 8-step tables */
   int *part = (int *)(smem + L.part);
@@ -2548,7 +2389,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   int xpar = 0;     /* parity of the double-buffered exact-delta term lists */
   __syncthreads();
 
-  build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane, !SHT || wave == 0);   /* (SHT: read after the phase-A barrier) */
+  build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane, !GM || wave == 0);   /* (GM: read after the phase-A barrier) */
   for (int m = olo + tid; m < ohi; m += TB) col_pre_build(pre + m, P + m, M, NW, PS);   /* own columns */
   {
     const int hl0 = (lane < nh) ? hp[lane] : 0;   /* loaded with every lane active */
@@ -2573,7 +2414,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       const int tid = tid_sw, lane = tid & 63;
       const int hf = PR ? (tid & 1) : 0, tx = PR ? (tid >> 1) : tid;
       const int mt = olo + tx;
-      const int ckslot = (SP && !LCK) ? half * TB + tid : tid;   /* this thread's Gibbs checkpoint slots */
+      const int ckslot = SP ? half * TB + tid : tid;   /* this thread's Gibbs checkpoint slots */
       (void)hf; (void)mt; (void)ckslot;
       const bool want_logl = (sw == A.spc - 1);
       /* this sweep's lane-parallel proposal tables, filled cooperatively (one entry per thread) before the
@@ -2583,7 +2424,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
          own copy as before (ptab_fill).  The previous sweep's readers are past the end-of-sweep barrier. */
       uint32_t tblk = 0u, toff = 0u;
       bool tvalid = false;
-      if constexpr (!MCD && !GM && SR_COOP_TABLES) {   /* (GM: its registers spill 37 more VGPRs, r05l) */
+      if constexpr (!MCD && !GM) {   /* (GM: its registers spill 37 more VGPRs, r05l) */
         if (8 + 2 * M + SR_RNG_SLACK <= (SR_RING - 1) * SR_MT_N - (SR_MT_N - 1)) {
           rng_ensure(R, 8 + 2 * M + SR_RNG_SLACK, tid, TB);
           const uint32_t sp = R.off + 8u + 2u * (uint32_t)M;
@@ -2601,8 +2442,6 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           tvalid = true;
         }
       }
-      /* the c, d draws' ziggurat steps, before the phase-A barrier (their table loads overlap the wait) */
-      const CDPre cdpf = (SR_CD_PREFETCH && !MCD && !GM) ? cd_prefetch(R, lane) : CDPre{};
       FST(15);
       /* ============ phase A: totals and the c, d draws (mcmc.c:768-825) */
       {
@@ -2656,7 +2495,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                      const bool ok2 = draw_cd_fast(R2, c2, d2, s3 + z, s0, s1, s2, tb, lane);
                      c += (ok2 ? c2 : 1.0) * (double)z; d += d2 * (double)z;
                      return false; }()) {
-        } else if (!draw_cd_fast(R, c, d, s3, s0, s1, s2, tb, lane, cdpf)) {
+        } else if (!draw_cd_fast(R, c, d, s3, s0, s1, s2, tb, lane)) {
           if (tid == 0) misc[MS_CDSEQ]++;
           double cd2[2] = {c, d};
           for (int k = 0; k < 2; ++k)
@@ -2696,7 +2535,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
         }
       }
       /* PR: one shared copy of the tables, built by waves 0-4 (T8 quarters, T4), then a barrier */
-      if ((PR ? wave == 4 : (!SHT || wave == NWV - 1)) && lane < 16) {   /* per-wave (PR, SHT: shared) tables for 4 walk entries with bits = lane */
+      if ((PR ? wave == 4 : (!GM || wave == NWV - 1)) && lane < 16) {   /* per-wave (PR, GM: shared) tables for 4 walk entries with bits = lane */
         double sc[5];
         const double pr = t4_row(lane, rA, rB, sc);
 #pragma unroll
@@ -3003,7 +2842,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
              phase C starts inside it and the entry is on the fast path, else by the scalar path */
           if (p0 == 0) {
             const int dlt = tvalid ? (int)((rblk - tblk) * SR_MT_N + roff) - (int)toff : -1;
-            const uint32_t e = (SR_COOP_TABLES && dlt >= 0 && dlt < 128) ? ptab[512 + dlt] : 0u;
+            const uint32_t e = (dlt >= 0 && dlt < 128) ? ptab[512 + dlt] : 0u;
             if ((e >> 25) & 1u) {
               const bool veto = (e >> 24) & 1u;
               const int i = (int)(e & 4095u);
@@ -3021,9 +2860,9 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
               (void)scalar_one(0);
             }
           }
-          /* (the swap in one batch with proposals 1..15 measured no faster at round 3: profiles/r03e_ab_phasec.json;
-             SR_MERGE_SWAP re-tests it) */
-          if (p0 > 0 || (SR_MERGE_SWAP && (!GM || SR_MERGE_SWAP_GM) && pend == 1)) {
+          /* a fast-path swap is drawn into one batch with proposals 1..15 (its acceptance, ~44 %, then wastes their
+             terms; not in the HBM-column kernels, whose proposal terms cost far more) */
+          if (p0 > 0 || (!GM && pend == 1)) {
             /* Lane-parallel draws: lane l evaluates "a pi1 / pi2 / pi3 proposal starting at word
                offset o" for o = l and o = l + 64 (words o..o+4) into ptab; the scan below then walks
                the batch's actual offsets reading those results.  ok = no GSL rejection and a nonzero
@@ -3135,7 +2974,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           const HM hb1 = hbc;
           /* every thread owns a taxon when the shape is compiled in and fills the block (the bench kernel): the
              ownership test is then a constant, not an exec mask re-set around every slot */
-          constexpr bool ALLOWN = SR_OWN_CONST && !SP && !PR && SR_FM > 0 && SR_FM >= TB;
+          constexpr bool ALLOWN = !SP && !PR && SR_FM > 0 && SR_FM >= TB;
           const bool own = ALLOWN || mt < ohi;
           if (one && own) { a1 = sab[mt]; b1 = sab[M + mt]; }
           FST(13);
@@ -3167,7 +3006,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                 q.Kn = hf ? qb.Kn : qa.Kn; q.r0 = hf ? qb.r0 : qa.r0;
                 int d0 = 0, d1 = 0;
                 if ((hf ? vb : va) && tx < M)
-                  taxon_dt(prop_kind(pa), q, a1, b1, P + tx, pre + tx, M, hb1, hcnt, nhall, d0, d1, hbx, N, PS);
+                  taxon_dt(prop_kind(pa), q, a1, b1, P + tx, pre + tx, M, hb1, hcnt, nhall, d0, d1, hbx, PS);
                 int Xa0, Xa1, Ya, Xb0, Xb1, Yb;
                 if (prop_kind(pa) == PK_PI1) {   /* dt in {-1, 0, 1}, dt0 dt1 = 0: ballot counts per parity */
                   const uint64_t p0m = __ballot(d0 > 0), n0m = __ballot(d0 < 0);
@@ -3196,29 +3035,13 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                kind prop_kind(s), so each copy holds one kind's code and the slots' loads, ALU
                and reductions are independent */
             int d0s[16], d1s[16];
-            /* the sweep's main batch (proposals 1..15 all drawn): every slot unconditionally, vetoed slots and
-               lanes without a taxon masked afterwards, so no branch separates the slots' reads (a lane without a
-               taxon reads the half's last column: in range in LDS and in HBM) */
-            const bool full = SR_FULL_BATCH && p0 == 1 && pend == 16;
-            if (full) {
-              d0s[0] = 0; d1s[0] = 0;
-              const int mtc = min(mt, ohi - 1);
-#pragma unroll
-              for (int sI = 1; sI < 16; ++sI) {
-                const Prop q = load_prop(sI);
-                int dt0 = 0, dt1 = 0;
-                taxon_dt(prop_kind(sI), q, a1, b1, P + mtc, pre + mtc, M, hb1, hcnt, nhall, dt0, dt1, hbx, N, PS);
-                const bool use = mt < ohi && !vetoed(sI);
-                d0s[sI] = use ? dt0 : 0; d1s[sI] = use ? dt1 : 0;
-              }
-            } else {
 #pragma unroll
             for (int sI = 0; sI < 16; ++sI) {
               d0s[sI] = 0; d1s[sI] = 0;
               if (sI >= p0 && sI < pend && !vetoed(sI)) {
                 const Prop q = load_prop(sI);
                 int dt0 = 0, dt1 = 0;
-                if (own) taxon_dt(prop_kind(sI), q, a1, b1, P + mt, pre + mt, M, hb1, hcnt, nhall, dt0, dt1, hbx, N, PS);
+                if (own) taxon_dt(prop_kind(sI), q, a1, b1, P + mt, pre + mt, M, hb1, hcnt, nhall, dt0, dt1, hbx, PS);
                 d0s[sI] = dt0; d1s[sI] = dt1;
               }
             }
@@ -3229,11 +3052,10 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                 if (sI >= p0 && sI < pend && !vetoed(sI)) {
                   const Prop q = load_prop(sI);
                   int dt0 = 0, dt1 = 0;
-                  if (mt < ohi) taxon_dt(prop_kind(sI), q, a1 + z, b1, P + mt, pre + mt, M, hb1, hcnt, nhall, dt0, dt1, hbx, N, PS);
+                  if (mt < ohi) taxon_dt(prop_kind(sI), q, a1 + z, b1, P + mt, pre + mt, M, hb1, hcnt, nhall, dt0, dt1, hbx, PS);
                   d0s[sI] |= dt0 & z; d1s[sI] |= dt1 & z;
                 }
               }
-            }
             }
             FST(3);
             if (SR_TSUMS && !GM && pack && pend - p0 >= SR_TSUMS) {   /* (GM: see below) */
@@ -3292,7 +3114,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
             } else {
 #pragma unroll
             for (int sI = 0; sI < 16; ++sI) {
-              if (full ? sI >= 1 : (sI >= p0 && sI < pend && !vetoed(sI))) {   /* (full: vetoed sums unread) */
+              if (sI >= p0 && sI < pend && !vetoed(sI)) {
                 int X0, X1, Y0, Y1;
                 if (prop_kind(sI) == PK_PI1) {   /* pi1: dt in {-1, 0, 1} and dt0 dt1 = 0: every sum is a ballot count */
                   const int cp0 = (int)__popcll(__ballot(d0s[sI] > 0)), cn0 = (int)__popcll(__ballot(d0s[sI] < 0));
@@ -3301,16 +3123,11 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                 } else if (pack) {   /* per-wave sums of (dt + N) fit 16-bit fields (N < 512) */
                   const uint32_t u1 = (uint32_t)wave_sum_i32((int)((uint32_t)(d0s[sI] + N) | ((uint32_t)(d1s[sI] + N) << 16)));
                   X0 = (int)(u1 & 0xffffu) - 64 * N; X1 = (int)(u1 >> 16) - 64 * N;
-#ifdef SR_EXACT_Y
-                  const uint32_t u2 = (uint32_t)wave_sum_i32((int)((uint32_t)abs(d0s[sI]) | ((uint32_t)abs(d1s[sI]) << 16)));
-                  Y0 = (int)(u2 & 0xffffu); Y1 = (int)(u2 >> 16);
-#else
                   /* the error bound needs only upper bounds of sum |dt0| and sum |dt1|: a reversal of
                      [ii, jj] changes a taxon's alive cells inside it only, |dt0| + |dt1| <= 2 (jj - ii + 1),
                      times the taxa with a nonzero change (one ballot instead of a second reduction) */
                   const Prop qb = load_prop(sI);
                   Y0 = Y1 = (int)__popcll(__ballot((d0s[sI] | d1s[sI]) != 0)) * 2 * (qb.jj - qb.ii + 1);
-#endif
                 } else {
                   X0 = wave_sum_i32(d0s[sI]); X1 = wave_sum_i32(d1s[sI]);
                   Y0 = wave_sum_i32(abs(d0s[sI])); Y1 = wave_sum_i32(abs(d1s[sI]));
@@ -3345,7 +3162,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                 if (sI >= p0 && sI < pend && !vetoed(sI)) {
                   const Prop q = load_prop(sI);
                   int dt0 = 0, dt1 = 0;
-                  if (mv) taxon_dt(prop_kind(sI), q, a, b, P + m, pre + m, M, hb, hcnt, nhall, dt0, dt1, hbx, N, PS);
+                  if (mv) taxon_dt(prop_kind(sI), q, a, b, P + m, pre + m, M, hb, hcnt, nhall, dt0, dt1, hbx, PS);
                   x0s[sI] += dt0; x1s[sI] += dt1; ys[sI] += abs(dt0) + abs(dt1);
                 }
               }
@@ -3480,14 +3297,14 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
             const int a = sab[m], b = sab[M + m];
             int dt0, dt1;
             taxon_dt(kind, q, a, b, Pm, prem, M, kind == PK_PI3 ? hard_bits_col<HM>(Pm, M, hl, nh) : (HM)0, hcnt, nhall, dt0, dt1,
-                     hbx, N, PS);
+                     hbx, PS);
             /* every read of the taxon's state before its first write (the compiler cannot tell the LDS / HBM
                arrays apart, so a read after a write waits for it: one round trip instead of one per access) */
             const int k0 = scnt[m], k1 = scnt[M + m], k2 = scnt[2 * M + m], k3 = scnt[3 * M + m];
             const int lo = min(i, j), hi = max(i, j), wl = lo >> 5, wh = hi >> 5;
             /* pi1 over at most 8 words (always at N <= 256): the words [wl - 1, wh + 1], the moved bit and the
                prefix below word wl read now; the shifted words and their prefix entries computed in registers */
-            const bool reg1 = SR_APPLY_REG && (!GM || SR_GM_APPLY_REG) && kind == PK_PI1 && wh - wl < 8;   /* (GM: SR_GM_APPLY_REG) */
+            const bool reg1 = !GM && kind == PK_PI1 && wh - wl < 8;   /* (GM: its registers spilled 37 more VGPRs, r05l) */
             uint32_t wv[10];
             uint32_t vb = 0u;
             int sbase = 0;
@@ -3653,25 +3470,11 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           FST(10);
           /* the hard tables only when a hard site moved (the columns' hard-site bits never change) */
           if (hmoved) {   /* (block-uniform: every wave holds the same hard positions) */
-            if constexpr (SHT) SR_SYNC(); else wsync();   /* SHT: every wave is past its reads of the shared tables */
-            build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane, !SHT || wave == 0);
-            if constexpr (SHT) SR_SYNC();                 /* ... and the next batch reads the new ones */
-            if (SR_DOUBLE == 8 && !SHT) { wsync(); build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane); }
-            tvalid = false;
-            if (SR_COOP_TABLES > 1 && p0 < 16) {
-              /* the proposal tables depend on the hard positions: refilled here by all threads at the next
-                 batch's start (every wave is past this batch's table reads: the terms barrier), one barrier
-                 instead of each wave refilling its own copy */
-              rng_ensure(R, 133, tid, TB);
-              tblk = R.blk;
-              toff = R.off;
-              const uint32_t sbase = (tblk & (SR_RING - 1)) * SR_MT_N + toff;
-              const int savail = min((int)((R.gen - tblk) * SR_MT_N - toff), 128);
-              for (int k = tid; k < 3 * 128; k += TB)
-                ptab_fill(ptab, ring, sbase, savail, k & 127, k >> 7, N, nh, hcnt, nhall, mdN, mdN1, md2, mdH, mdH1);
-              SR_SYNC();
-              tvalid = true;
-            }
+            if constexpr (GM) SR_SYNC(); else wsync();   /* GM: every wave is past its reads of the shared tables */
+            build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane, !GM || wave == 0);
+            if constexpr (GM) SR_SYNC();                  /* ... and the next batch reads the new ones */
+            if (SR_DOUBLE == 8 && !GM) { wsync(); build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane); }
+            tvalid = false;   /* (the proposal tables depend on the hard positions) */
           }
           FST(9);
           wsync();
@@ -3781,7 +3584,7 @@ __constant__ unsigned long long sr_spec_abi[4] = {
 
 struct srk_dev {
   int device, N, M, NW, nh, nchains, TB, TPT, rec_cap, gm, pr, sp, grid, coop;
-  int lck;                 /* split kernels: Gibbs checkpoints in LDS (LK kernels) */
+  int lpre;                /* split kernels: the own half's column prefixes in LDS (LPRE kernels) */
   int mcd;                 /* manycd: per-taxon c, d (MCD kernels) */
   int jit;                 /* the launch uses the shape-specialised kernel (srk_spec_load) */
   int jemb;                /* ... and its code object is the one embedded in the library */
@@ -3817,7 +3620,7 @@ static bool sr_pair_ok(int N, int M)
 }
 
 static sr_kfn sr_pick_kernel(int TB, int N, int M, bool gm, bool pr, int nh, bool sp = false, bool mcd = false,
-                             bool lk = false)
+                             bool lpre = false)
 {
   if (mcd) {   /* manycd: the generic one-workgroup kernels at 1024 threads */
     if (TB != 1024 || pr || sp) return nullptr;
@@ -3826,19 +3629,16 @@ static sr_kfn sr_pick_kernel(int TB, int N, int M, bool gm, bool pr, int nh, boo
   }
   if (pr) return (TB == 1024 && !gm) ? (sr_kfn)sr_sweep_kernel<1024, 9, false, true> : nullptr;
 #ifndef SR_STAMPS
-  if (sp) {   /* LK: checkpoints in LDS (where the layout fits them), else in HBM scratch */
+  if (sp) {   /* lpre: the own half's column prefixes in LDS (where the layout fits them), else in HBM scratch */
     if (!gm) return nullptr;
-    if (TB == 1024) return lk ? (sr_kfn)sr_sweep_kernel<1024, 0, true, false, true, false, true>
+    if (TB == 1024) return lpre ? (sr_kfn)sr_sweep_kernel<1024, 0, true, false, true, false, true>
                               : (sr_kfn)sr_sweep_kernel<1024, 0, true, false, true>;
-    if (TB == 512) return lk ? (sr_kfn)sr_sweep_kernel<512, 0, true, false, true, false, true>
+    if (TB == 512) return lpre ? (sr_kfn)sr_sweep_kernel<512, 0, true, false, true, false, true>
                              : (sr_kfn)sr_sweep_kernel<512, 0, true, false, true>;
     return nullptr;
   }
 #else
   if (sp) return nullptr;   /* (stamp builds index their counters by block) */
-#endif
-#ifdef SR_PAIR_ONLY   /* register-pressure experiments: compile the pair kernel alone */
-  return nullptr;
 #endif
   if (gm) {
     if (TB == 256) return (sr_kfn)sr_sweep_kernel<256, 0, true>;
@@ -4071,12 +3871,12 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
     const char *e = getenv("SR_SPLIT");
     const int want = e ? atoi(e) : -1;
     const int Mh = sr_sp_half(st->M);
-    /* the split kernels' own layout: Gibbs checkpoints in LDS where they fit (SR_SP_LCK; up to N ~ 1300 at 1024
-       threads), else in HBM scratch (round 4's form; any N) */
-    const size_t lds_lk = sr_layout(st->N, st->M, st->NW, TB, true, false, st->nh, true).total;
-    const bool lk = SR_SP_LCK && lds_lk <= 160 * 1024;
-    const size_t lds_sp = lk ? lds_lk : sr_layout(st->N, st->M, st->NW, TB, true, false, st->nh, false).total;
-    sr_kfn ks = sr_pick_kernel(TB, st->N, st->M, true, false, st->nh, true, false, lk);
+    /* the split kernels' own layout: the own half's column prefixes in LDS where they fit (up to N ~ 1300 at 1024
+       threads), else in HBM scratch (any N) */
+    const size_t lds_lpre = sr_layout(st->N, st->M, st->NW, TB, true, false, st->nh, true).total;
+    const bool lpre = lds_lpre <= 160 * 1024;
+    const size_t lds_sp = lpre ? lds_lpre : sr_layout(st->N, st->M, st->NW, TB, true, false, st->nh, false).total;
+    sr_kfn ks = sr_pick_kernel(TB, st->N, st->M, true, false, st->nh, true, false, lpre);
     if (lds_sp > 160 * 1024) ks = nullptr;
     /* SR_SPLIT=2 (experiment, opt-in only): 512-thread halves of up to two blocks' taxa, several taxa per
        thread (256 VGPRs, 8 waves per CU; measured slower) -- never chosen without it */
@@ -4091,7 +3891,7 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
           hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)ks, TB, lds_sp) == hipSuccess &&
           grid <= occ * cus) {
         d->sp = 1;
-        d->lck = lk ? 1 : 0;
+        d->lpre = lpre ? 1 : 0;
         d->grid = grid;
         d->lds = lds_sp;
         /* SR_COOP=0: an ordinary launch of the same grid (rocprofv3's kernel tracer crashes at
@@ -4123,12 +3923,7 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
   if (pkey) rc |= dev_alloc_copy(d, &A.pkey, pkey, C * 2);
   if (d->gm) {
     rc |= dev_alloc_copy(d, &A.gpre, (const uint16_t *)nullptr, C * sr_gm_pre(st->M, st->NW));
-    using CKT = typename std::conditional<SR_CK32 != 0, float, double>::type;
-    CKT *gck = nullptr;
-    /* (split kernels with their checkpoints in LDS: no HBM scratch) */
-    rc |= dev_alloc_copy(d, &gck, (const CKT *)nullptr,
-                         C * (d->sp ? ((d->lck && !SR_SP_LPRE) ? 0 : sr_sp_ck(st->N, TB)) : sr_gm_ck(st->N, st->M, TB)));
-    A.gck = gck;
+    rc |= dev_alloc_copy(d, &A.gck, (const double *)nullptr, C * (d->sp ? sr_sp_ck(st->N, TB) : sr_gm_ck(st->N, st->M, TB)));
     rc |= dev_alloc_copy(d, &A.glbuf, (const double *)nullptr, C * st->M);
     rc |= dev_alloc_copy(d, &A.gcbuf, (const double *)nullptr, C * sr_gm_cbuf(st->M));
   }
@@ -4143,7 +3938,7 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
     rc |= dev_alloc_copy(d, &A.xerr, (const int *)nullptr, 1);
   }
   if (rc) { srk_destroy(d); return -5; }
-  sr_kfn k = sr_pick_kernel(TB, st->N, st->M, d->gm != 0, d->pr != 0, st->nh, d->sp != 0, d->mcd != 0, d->lck != 0);
+  sr_kfn k = sr_pick_kernel(TB, st->N, st->M, d->gm != 0, d->pr != 0, st->nh, d->sp != 0, d->mcd != 0, d->lpre != 0);
   if (hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->lds) != hipSuccess) {
     srk_destroy(d);
     return -5;
@@ -4174,7 +3969,7 @@ extern "C" int srk_run(srk_dev *d, int calls, int spc, int save, int rec_base)
   HIPCHK(hipSetDevice(d->device));
   KArgs A = d->args;
   A.calls = calls; A.spc = spc; A.save = save; A.rec_base = rec_base;
-  sr_kfn k = sr_pick_kernel(d->TB, d->N, d->M, d->gm != 0, d->pr != 0, d->nh, d->sp != 0, d->mcd != 0, d->lck != 0);
+  sr_kfn k = sr_pick_kernel(d->TB, d->N, d->M, d->gm != 0, d->pr != 0, d->nh, d->sp != 0, d->mcd != 0, d->lpre != 0);
   if (d->sp) HIPCHK(hipMemsetAsync(A.xflag, 0, (size_t)d->nchains * 2 * sizeof(int), d->stream));   /* exchange sequence restarts */
   if (d->have_events) HIPCHK(hipEventRecord(d->ev0, d->stream));
   if (d->jit) {   /* the run-time specialised kernel (same arguments; LDS columns: one workgroup per chain) */
@@ -4584,8 +4379,11 @@ __global__ void __launch_bounds__(64) sr_gibbs_selftest_kernel(const uint32_t *P
     }
     res = draw_fast_s<NWM>(wk, Pm, M, N, rev, o, L, POo, u, K, tb, vA, vB, T4w, T8w, (uint64_t *)(fb + m), d0, e0, d1, e1);
   } else {
+#ifdef SR_STAMP_GIBBS
+    unsigned long long st_acc[16] = {0}, st_t = 0;   /* (draw_fast's phase stamps: unread here) */
+#endif
     res = draw_fast<MODE == 3>(Pm, prem, M, N, NW, rev, o, L, POo, u, K, tb, vA, vB, rA, rB, T4w, T8w, cks + m, M, 0,
-                               (uint64_t *)(fb + m), d0, e0, d1, e1);
+                               (uint64_t *)(fb + m), d0, e0, d1, e1 GSTAMP_PASS);
   }
   int *r = out + 5 * m;
   r[0] = res; r[1] = d0; r[2] = e0; r[3] = d1; r[4] = e1;
