@@ -352,6 +352,26 @@ __device__ __forceinline__ void rng_ensure(DRng &r, int n, int t, int nthr)
   while (r.gen <= last) rng_gen<false>(r, t, nthr);
 }
 
+/* One more MT19937 block in one dependency phase (sr_mt_block_word: every word from block gen - 1 alone), written
+ * by the whole workgroup with no barrier of its own: the caller's next workgroup barrier publishes it, so at most
+ * one call between two barriers.  The slot it overwrites holds block gen - SR_RING, which must be dead in every
+ * wave: no thread reads the ring more than `back` blocks below the caller's cursor between the barrier before this
+ * call and the one after it (the sweep kernel's call sites say why).  The new block's slot differs from its
+ * source's, and nobody reads a block >= gen before the barrier.  Block-uniform condition, from the cursor alone (no
+ * register carried through the sweep); the Philox stream keeps rng_gen_block. */
+template <int TB>
+__device__ __forceinline__ void rng_topup(DRng &r, uint32_t back, int t)
+{
+  const uint32_t gen = __builtin_amdgcn_readfirstlane(r.gen);
+  if (r.ph || gen + back - __builtin_amdgcn_readfirstlane(r.blk) >= SR_RING) return;
+  const uint32_t *prev = r.ring + ((gen - 1) & (SR_RING - 1)) * SR_MT_N;
+  uint32_t *nxt = r.ring + (gen & (SR_RING - 1)) * SR_MT_N;
+#pragma unroll
+  for (int k0 = 0; k0 < SR_MT_N; k0 += TB)
+    if (k0 + TB <= SR_MT_N || k0 + t < SR_MT_N) nxt[k0 + t] = sr_mt_block_word(prev, k0 + t);
+  r.gen = gen + 1;
+}
+
 /* word at relative offset j from the cursor (must be resident) */
 __device__ __forceinline__ uint32_t rng_peek(const DRng &r, uint32_t j)
 {
@@ -2453,6 +2473,9 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       }
       STAMP(0);
       FST(11);
+      /* one more ring block, published by the phase-A barrier: since the end-of-sweep barrier every wave read the ring
+         from the sweep's cursor on (the proposal tables above; rng_ensure's own refills end with a barrier) */
+      if constexpr (!GM && !PR && !MCD) rng_topup<TB>(R, 0u, tid);
       SR_SYNC();
       FST(11);
       {
@@ -3181,6 +3204,10 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
             STAMP_K(PK_PI3);
           }
           FST(4);
+          /* one more ring block, published by the batch barrier: since the batch barrier before this one every wave
+             read the ring from this batch's cursor on.  Not in the sweep's first batch: a wave may still be reading its
+             c, d and Gibbs words, which start a variable distance below (the sequential c, d draws). */
+          if constexpr (!GM && !PR && !MCD) { if (p0 > 0) rng_topup<TB>(R, 0u, tid); }
           SR_SYNC();
           if constexpr (SP) {   /* this half's sums of the batch's proposals (lane p of wave 0), exchanged */
             if (wave == 0 && lane >= p0 && lane < pend && lane < 16 && !((vpk >> 26) & 1)) {
@@ -3483,6 +3510,9 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       }
       STAMP(7);
       FST(0);
+      /* ... and one published by the end-of-sweep barrier: since the last batch barrier no wave read the ring at all
+         (decisions and moves), and the cursor moved by that batch's words (at most 128: `avail`) */
+      if constexpr (!GM && !PR && !MCD) rng_topup<TB>(R, 1u, tid);
       SR_SYNC();
       FST(11);
       }

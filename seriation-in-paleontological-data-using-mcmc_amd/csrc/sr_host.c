@@ -56,6 +56,22 @@ SR_API const char *sr_strerror(int code)
 
 SR_API int sr_device_count(void) { return srk_device_count(); }
 
+/* Test hook (tests/test_rng_block.py, not part of the public header): blocks 1..nblocks of the MT19937 stream
+   seeded with `seed` (raw, untempered words, 624 per block), by the sequential recurrence into seq and, each from
+   the sequential block before it, by the one-phase form the sweep kernels top their ring up with into one. */
+SR_API int sr_host_mt_block(unsigned long seed, int nblocks, uint32_t *seq, uint32_t *one)
+{
+  if (nblocks < 0 || !seq || !one) return SR_EINVAL;
+  uint32_t prev[SR_MT_N];
+  sr_mt_seed_block(prev, seed);
+  for (int b = 0; b < nblocks; b++) {
+    sr_mt_next_block(prev, seq + (size_t)b * SR_MT_N);
+    for (int k = SR_MT_N - 1; k >= 0; k--) one[(size_t)b * SR_MT_N + k] = sr_mt_block_word(prev, k);   /* any order */
+    memcpy(prev, seq + (size_t)b * SR_MT_N, sizeof prev);
+  }
+  return SR_OK;
+}
+
 /* ------------------------------------------------------- GSL_RNG_TYPE / GSL_RNG_SEED */
 /* gsl_rng_env_setup's contract (GSL 2.6 rng/env.c; the reference's mcmc_init calls it, mcmc.c:591-592): the
    generator named by GSL_RNG_TYPE out of gsl_rng_types_setup's list (rng/types.c, in its order), MT19937 when

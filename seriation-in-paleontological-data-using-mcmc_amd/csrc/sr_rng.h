@@ -102,6 +102,35 @@ SR_RHD void sr_mt_next_block(const uint32_t *prev, uint32_t *next)
   next[SR_MT_N - 1] = sr_mt_mix(prev[SR_MT_N - 1], next[0], next[SR_MT_M - 1]);
 }
 
+/* The twist in one dependency phase: word k of next = twist(prev) from prev alone, so that the words of a block
+ * can be produced by as many lanes with no ordering among them.  next[k] for k >= 227 needs next[k - 227], which
+ * is recomputed from prev (one level for k < 454, two above); word 623 needs next[0] and next[396].  At most four
+ * sr_mt_mix per word (word 623), 1192 for the block against the recurrence's 624. */
+SR_RHD uint32_t sr_mt_block_word(const uint32_t *prev, int k)
+{
+  const int D = SR_MT_N - SR_MT_M;   /* 227 */
+  if (k == SR_MT_N - 1) {
+    const uint32_t n0 = sr_mt_mix(prev[0], prev[1], prev[SR_MT_M]);
+    const uint32_t n169 = sr_mt_mix(prev[SR_MT_M - 1 - D], prev[SR_MT_M - D], prev[2 * SR_MT_M - 1 - D]);
+    const uint32_t n396 = sr_mt_mix(prev[SR_MT_M - 1], prev[SR_MT_M], n169);
+    return sr_mt_mix(prev[SR_MT_N - 1], n0, n396);
+  }
+  uint32_t far;
+  if (k < D) far = prev[k + SR_MT_M];
+  else if (k < 2 * D) far = sr_mt_mix(prev[k - D], prev[k - D + 1], prev[k - D + SR_MT_M]);
+  else {
+    const uint32_t f2 = sr_mt_mix(prev[k - 2 * D], prev[k - 2 * D + 1], prev[k - 2 * D + SR_MT_M]);
+    far = sr_mt_mix(prev[k - D], prev[k - D + 1], f2);
+  }
+  return sr_mt_mix(prev[k], prev[k + 1], far);
+}
+
+/* next = twist(prev) word by word in any order (prev and next distinct): equal to sr_mt_next_block */
+SR_RHD void sr_mt_next_block_1p(const uint32_t *prev, uint32_t *next)
+{
+  for (int k = 0; k < SR_MT_N; k++) next[k] = sr_mt_block_word(prev, k);
+}
+
 /* ------------------------------------------------------------------ host stream */
 typedef struct {
   uint32_t blk[SR_MT_N];  /* raw words of block `bidx` */

@@ -169,6 +169,7 @@ def _lib():
         "sr_host_run_sub": (ctypes.c_long, [P(c_double), c_double, ctypes.c_long]),
         "sr_host_philox": (None, [P(ctypes.c_uint32), P(ctypes.c_uint32), P(ctypes.c_uint32)]),
         "sr_host_mt_untemper": (None, [P(ctypes.c_uint32), ctypes.c_long, P(ctypes.c_uint32), P(ctypes.c_uint32)]),
+        "sr_host_mt_block": (c_int, [ctypes.c_ulong, c_int, P(ctypes.c_uint32), P(ctypes.c_uint32)]),
         "sr_host_initial_checkpoint": (c_int, [P(sr_dataset), P(sr_chain_spec), c_i32, ctypes.c_char_p]),
         "sr_host_init_chain": (c_int, [P(sr_dataset), ctypes.c_uint64, P(c_i32), P(c_i32), P(c_i32),
                                        P(c_double), P(ctypes.c_uint64)]),
