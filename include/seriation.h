@@ -193,15 +193,15 @@ int sr_session_debug_flagged(const sr_session *s, int32_t chain);
 double sr_session_last_kernel_ms(sr_session *s);
 int32_t sr_session_block_threads(const sr_session *s);
 /* Kernel variant the session runs: 0 = occurrence columns in LDS, one thread per taxon; 1 = columns
- * in HBM (chosen when the LDS layout exceeds 160 KB, e.g. 1024 sites x 2048 taxa); 2 = columns in
- * LDS, two lanes per taxon (the pair kernel: walks of <= 9 words and 257..512 taxa; opt-in with
- * SR_KERNEL=pair in the environment and block_threads unset -- slower than variant 0);
+ * in HBM (chosen when the LDS layout exceeds 160 KB, e.g. 1024 sites x 2048 taxa); 2 is no longer
+ * returned (it was the retired pair kernel, two lanes per taxon: slower than variant 0, DESIGN.md
+ * "Retired experiments");
  * 3 = columns in HBM, split chains: two co-resident workgroups per chain, each owning half of the
  * taxa (1024 threads, 1025..2048 taxa, grid co-resident; SR_SPLIT=0 in the environment disables it). */
 int32_t sr_session_variant(const sr_session *s);
 /* 1 when the session's launches use the sweep kernel compiled for its exact shape (sites, taxa, hard
  * sites fixed at compile time) -- the default for sessions with occurrence columns in LDS (variant 0) --
- * 0 for the generic kernel (HBM columns, the pair kernel, SR_F_GENERIC_KERNEL / SR_JIT=0, or the
+ * 0 for the generic kernel (HBM columns, SR_F_GENERIC_KERNEL / SR_JIT=0, or the
  * specialised code object unavailable: one stderr line says why).  Results are identical either way. */
 int32_t sr_session_specialized(const sr_session *s);
 /* Prepare the shape-specialised kernel a session of this dataset and opts (block_threads, SR_F_*_COLUMNS,

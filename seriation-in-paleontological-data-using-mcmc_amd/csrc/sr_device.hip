@@ -1,7 +1,7 @@
 /*
  * sr_device.hip -- the MI355X (gfx950) sweep kernel and the device session layer.
  *
- * One workgroup = one chain; one thread owns taxa m = tid + k*TB (k < TPT).  Everything a
+ * One workgroup = one chain; one thread owns taxa m = tid + k*TB.  Everything a
  * sweep touches lives on chip for the whole launch:
  *   registers: per-taxon a, b, t0, f0, t1, f1 (owned taxa); the hard-site positions
  *              (uniform); c, d, log(1-e^c), log(1-e^d); RNG cursor (uniform)
@@ -85,7 +85,7 @@ struct KArgs {
 #ifndef SR_CKG
 #define SR_CKG 4
 #endif
-/* test builds: every certification margin -- the Gibbs picks' REL / ABS (draw_fast, walk_pick_s, draw_pair9) and
+/* test builds: every certification margin -- the Gibbs picks' REL / ABS (draw_fast, walk_pick_s) and
    phase C's Eb (pc_classify) -- scaled by 2^-SR_CERT_SHIFT.  The product is 0; the negative control of
    tests/test_gpu_cert.py builds the library at 8 and must then see wrong picks and decisions, which shows that the
    self-tests (sr_device_selftest_gibbs / _decide) can see an understated bound. */
@@ -108,19 +108,6 @@ __device__ __forceinline__ const KArgs &kargs_late(const KArgs &A) { return A; }
 #ifndef SR_BATCH_MAX
 #define SR_BATCH_MAX 16
 #endif
-/* diagnostic builds (tools/build_variant.sh): SR_DOUBLE = k does phase k's work twice, the second result folded
-   in through an opaque zero (the chain is unchanged), so the time difference is the phase's marginal cost:
-   1 proposal terms, 2 proposal sums, 3 Gibbs draws, 4 the c, d draws, 5 K and the step tables, 7 the sweep's
-   table fill, 8 the hard-site tables after a hard site moved */
-#ifndef SR_DOUBLE
-#define SR_DOUBLE 0
-#endif
-__device__ __forceinline__ int sr_opaque_zero()
-{
-  int z;
-  __asm__ volatile("s_mov_b32 %0, 0" : "=s"(z));
-  return z;
-}
 
 /* ---------------------------------------------------------------- LDS carve */
 struct Lay {
@@ -143,21 +130,22 @@ __host__ __device__ static constexpr inline int sr_ckstride(int M, int TB) { ret
 /* gm: the global-memory variant (columns too large for LDS, e.g. 1024 x 2048): the per-taxon
  * arrays (P, pre, ck, a/b, counts, logl terms, exact-delta terms) live in HBM (chain-private,
  * owner-thread access, L2/MALL-resident) and get no LDS slot */
-/* taxa per exact-delta chunk (one wave's taxa): 64, or 32 in the pair kernels (two lanes per taxon) */
-__host__ __device__ static constexpr inline int sr_chunk(bool pr) { return pr ? 32 : 64; }
+/* taxa per exact-delta chunk (one wave's taxa).  A function, not a literal: with a plain 64 in the chunk arithmetic
+   the generic one-workgroup kernels come out with the same opcodes in other scalar registers, and the removal of
+   the pair kernel (32-taxon chunks) was held to identical instructions ("Retired experiments") */
+__host__ __device__ static constexpr inline int sr_chunk() { return 64; }
 /* gm: one block-shared copy of the hard-site and 4-step tables (a copy per wave passed 160 KB at N ~ 1250 and 1024
  * threads; shared, N reaches 4095); lpre (split-chain kernels whose layout has room): the own half's column prefix
  * table in LDS (stride = the half's taxa) instead of HBM scratch */
-__host__ __device__ static constexpr inline Lay sr_layout(int N, int M, int NW, int TB, bool gm, bool pr = false, int nh = 0,
-                                                          bool lpre = false)
+__host__ __device__ static constexpr inline Lay sr_layout(int N, int M, int NW, int TB, bool gm, int nh = 0, bool lpre = false)
 {
   Lay L{};
   size_t o = 0;
-  const int CH = sr_chunk(pr), KT = (M + CH - 1) / CH, NWV = TB / 64;
+  const int CH = sr_chunk(), KT = (M + CH - 1) / CH, NWV = TB / 64;
   const size_t g = gm ? 0 : 1;
   lpre = lpre && gm;
-  /* step tables: one copy per wave, or one shared copy behind a barrier (pair kernels: 16 waves) */
-  const size_t NT = (pr || gm) ? 1 : NWV;
+  /* step tables: one copy per wave, or (gm) one shared copy behind a barrier */
+  const size_t NT = gm ? 1 : NWV;
   L.tab = o;   o = sr_al16(o + 512 * sizeof(double));   /* glibc exp/log tables */
   L.cbuf = o;  o = sr_al16(o + g * 2 * KT * CH * sizeof(double));       /* [2][KT*CH] by proposal parity */
   L.lbuf = o;  o = sr_al16(o + g * M * sizeof(double));
@@ -166,7 +154,7 @@ __host__ __device__ static constexpr inline Lay sr_layout(int N, int M, int NW, 
   L.rpi0 = o;  o = sr_al16(o + (size_t)N * 4);
   L.rpi1 = o;  o = sr_al16(o + (size_t)N * 4);
   L.ht = o;    o = sr_al16(o + (gm ? 1 : (size_t)NWV) * (2 * N + 2) * 2);   /* per wave (gm: shared): hcnt[N+1], nhall[N] (int16) */
-  const size_t rw = (pr || sr_regwalk(N, M, TB, gm, nh)) ? 1 : 0;   /* register walks (pair kernels too): byte tables instead of LDS checkpoints */
+  const size_t rw = sr_regwalk(N, M, TB, gm, nh) ? 1 : 0;   /* register walks: byte tables instead of LDS checkpoints */
   L.ck = o;    o = sr_al16(o + g * (1 - rw) * ((N >> 5) + 1) * sr_ckstride(M, TB) * sizeof(double));
   L.ccnt = o;  o = sr_al16(o + (size_t)2 * KT * 4);
   L.sab = o;   o = sr_al16(o + g * 2 * M * 4);
@@ -1445,220 +1433,6 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
   return res;
 }
 
-
-/* ---- pair kernels: two lanes per taxon ---------------------------------------------------
- * Lanes 2t and 2t+1 of a wave share taxon t; the even lane ("lo") holds walk words 0..4 of a
- * Gibbs draw, the odd lane ("hi") words 5..8 (walks of <= 9 words: N <= 287).  Partner values
- * travel by one DPP quad_perm [1,0,3,2] (lane ^ 1) each. */
-__device__ __forceinline__ int pair_swap_i32(int x) { return __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false); }
-__device__ __forceinline__ double pair_swap_f64(double v)
-{
-  const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint32_t lo = (uint32_t)pair_swap_i32((int)(uint32_t)b), hi = (uint32_t)pair_swap_i32((int)(uint32_t)(b >> 32));
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-
-/* draw_fast_s<9> (mcmc_auxa + mcmc_logtop + mcmc_randompick, certified) with the walk split over a
- * lane pair: each lane runs passes 0 and 1 over its five words; the hi lane's chain starts from
- * y' = 1 at word 5 and is rescaled by the lo lane's y at word 5 (S = S_lo + y5 S'_hi, checkpoints
- * S_lo + y5 ck'_k: a re-association of the same products, two more roundings per value -- inside
- * REL, which gains 8 units for them); pass 2 runs identically in both lanes on word j's data taken
- * from the lane that holds it.  wk: this lane's words 5h .. 5h+4 (word 9 = 0).  Both lanes return
- * the same pick and count deltas.  Call pair-uniformly (both lanes active). */
-__device__ __forceinline__ int draw_pair9(const uint32_t (&wk)[5], int h, const uint32_t *Pm, int M, int N, int NW, bool rev,
-                                          int o, int L, int POo, double u, const CD &K, const sr_mtab &tb, double vA,
-                                          double vB, const double *T4, const double *T8, uint64_t *fbk, int &dt0, int &df0,
-                                          int &dt1, int &df1)
-{
-  constexpr int NWM = 9, NH = 5;
-  const int k0 = NH * h;
-  const int nk = (L >> 5) + 1;
-  const int kl = L >> 5, nbl = (L & 31) + 1;
-  /* ---- pass 0: window of words that can hold mass above 2^-40 relative to entry o */
-  int Otot = 0;
-#pragma unroll
-  for (int i = 0; i < NH; ++i) Otot += __popc(wk[i]);
-  const int Op = pair_swap_i32(Otot);
-  int klo = NWM, khi = -1;
-  double qlo = 0.0;
-  uint32_t wl = 0u;
-  {
-    const double dv = vB - vA;
-    const double Fo = __builtin_fma((double)POo, dv, (double)o * vA);
-    int O = h ? Op : 0;
-    const uint32_t lastm = (2u << (L & 31)) - 1u;
-#pragma unroll
-    for (int i = 0; i < NH; ++i) {
-      const int k = k0 + i;
-      const bool full = k < kl;
-      const int nb = full ? 32 : nbl;
-      const uint32_t vm = full ? 0xffffffffu : lastm;
-      const double qs = Fo - __builtin_fma((double)O, dv, (double)(32 * k) * vA);
-      const int ones = __popc(wk[i] & vm);
-      const double ub = qs - (double)(nb - ones) * vA;
-      const bool in = (k < nk) && ub > -SR_WIN_T;
-      const bool first = in && klo == NWM;
-      qlo = first ? qs : qlo;
-      klo = first ? k : klo;
-      khi = in ? k : khi;
-      O += __popc(wk[i]);
-      wl = (k == kl) ? wk[i] : wl;
-    }
-    const int klo_p = pair_swap_i32(klo), khi_p = pair_swap_i32(khi);
-    const double qlo_p = pair_swap_f64(qlo);
-    const uint32_t wl_p = (uint32_t)pair_swap_i32((int)wl);
-    qlo = (klo <= klo_p) ? qlo : qlo_p;
-    klo = min(klo, klo_p);
-    khi = max(khi, khi_p);
-    wl |= wl_p;
-  }
-  /* ---- pass 1: my words' sums (lo: from y0; hi: relative to y = 1 at word 5), then combined */
-  const double y0 = exp2_split(qlo);
-  double S = 0.0;
-  double ckr[NH], yst[NH];
-  double y = h ? 1.0 : y0;
-  {
-    auto wload = [&](int i, double2 (&t)[4]) {
-      const int k = k0 + i;
-      const bool inw = k >= klo && k <= khi;
-      const int nfk = inw ? ((k < kl) ? 4 : (nbl >> 3)) : 0;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const uint32_t e = (g < nfk) ? ((wk[i] >> (8 * g)) & 255u) : 256u;
-        t[g] = *reinterpret_cast<const double2 *>(T8 + 2 * e);
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < NH; ++i) {
-      double2 t[4];   /* no read-ahead: four waves per SIMD cover the table reads' latency */
-      wload(i, t);
-      yst[i] = y;
-      {
-        const double w23 = __builtin_fma(t[2].y, t[3].x, t[2].x);
-        const double w13 = __builtin_fma(t[1].y, w23, t[1].x);
-        const double W = __builtin_fma(t[0].y, w13, t[0].x);
-        const double pw = (t[0].y * t[1].y) * (t[2].y * t[3].y);
-        S = __builtin_fma(y, W, S);
-        y = y * pw;
-      }
-      ckr[i] = S;
-    }
-    /* the partial byte (c8 entries), by the lane that holds its word, when it lies in the window */
-    const int nfull = (L + 1) >> 3, c8 = (L + 1) & 7, kb = nfull >> 2;
-    const bool actb = c8 > 0 && kb >= klo && kb <= khi && kb >= k0 && kb < k0 + NH;
-    const uint32_t eb = (wl >> (8 * (nfull & 3))) & 255u;
-    const double2 tlo = t4sp(T4, actb ? min(c8, 4) : 0, eb & 15u);
-    const double shi = t4s(T4, actb ? max(c8 - 4, 0) : 0, eb >> 4);
-    S = __builtin_fma(y, tlo.x, S);
-    S = __builtin_fma(y * tlo.y, shi, S);
-  }
-  const double S_p = pair_swap_f64(S), y_p = pair_swap_f64(y);
-  const double S_lo = h ? S_p : S, y5 = h ? y_p : y, S_hi = h ? S : S_p;
-  const double St = S_lo + y5 * S_hi;
-  {
-    const double cb = h ? S_lo : 0.0, cs = h ? y5 : 1.0;
-#pragma unroll
-    for (int i = 0; i < NH; ++i) { ckr[i] = cb + cs * ckr[i]; yst[i] = cs * yst[i]; }
-  }
-  /* ---- pass 2 (both lanes, identical data): word, byte, nibble, entry; certification */
-  int res = -1, POp = 0;
-  bool uf = false;   /* as draw_fast_s: a window word start below 2^-700 takes the exact path */
-#pragma unroll
-  for (int i = 0; i < NH; ++i) uf |= k0 + i >= klo && k0 + i <= khi && yst[i] < 0x1p-700;
-  uf = uf || pair_swap_i32(uf ? 1 : 0) != 0;
-  if (St > 0.0 && St < 0x1p1000 && !uf) {
-    const double inv = 1.0 / St;
-    const double REL = (double)(N + 41) * 0x1p-50 * SR_CERT_SCALE;
-    const double ABS = (double)(N + 1) * 0x1p-39 * SR_CERT_SCALE;
-    const double uS = u * St;
-    int jl = 0;
-#pragma unroll
-    for (int i = 0; i < NH; ++i) jl += (k0 + i < khi && ckr[i] < uS) ? 1 : 0;
-    int j = jl + pair_swap_i32(jl);
-    j = max(j, klo);
-    const int ij = j - k0, ijm = j - 1 - k0;
-    double cy = 0.0, csp = 0.0;
-    uint32_t cww = 0u;
-    int cO = h ? Op : 0;   /* ones among walk entries [0, 32 j) when I hold word j */
-#pragma unroll
-    for (int i = 0; i < NH; ++i) {
-      if (i == ij) { cy = yst[i]; cww = wk[i]; }
-      cO += (i < ij) ? __popc(wk[i]) : 0;
-      if (i == ijm) csp = ckr[i];
-    }
-    const double cy_p = pair_swap_f64(cy), csp_p = pair_swap_f64(csp);
-    const uint32_t cww_p = (uint32_t)pair_swap_i32((int)cww);
-    const int cO_p = pair_swap_i32(cO);
-    const bool own = ij >= 0 && ij < NH, ownm = ijm >= 0 && ijm < NH;
-    const double yj = own ? cy : cy_p, Sp0 = ownm ? csp : csp_p;
-    const uint32_t ww = own ? cww : cww_p;
-    const int Oj = own ? cO : cO_p;
-    const int w0 = 32 * j;
-    const int nb = min(32, L + 1 - w0);
-    const int nfb = nb >> 3, nlb = (nb + 7) >> 3;
-    double2 tb8[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) tb8[g] = *reinterpret_cast<const double2 *>(T8 + 2 * ((ww >> (8 * g)) & 255u));
-    double Bg[4], Yg[4];
-    int nbc = 0;
-    {
-      double acc = Sp0, yy = yj;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        Yg[g] = yy;
-        acc = __builtin_fma(yy, tb8[g].x, acc);
-        Bg[g] = acc;
-        yy = yy * tb8[g].y;
-        nbc += (g < nfb && acc < uS) ? 1 : 0;
-      }
-    }
-    const int bsel = min(nbc, nlb - 1);
-    double base_b = Sp0, y_b = yj;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      if (g == bsel) y_b = Yg[g];
-      if (g + 1 == bsel) base_b = Bg[g];
-    }
-    const uint32_t bv = (ww >> (8 * bsel)) & 255u;
-    const int ce = min(nb - 8 * bsel, 8), c_lo = min(ce, 4), c_hi = ce - c_lo;
-    const double2 tlo = t4sp(T4, c_lo, bv & 15u);
-    const double N0 = __builtin_fma(y_b, tlo.x, base_b);
-    const bool nsel = c_hi > 0 && N0 < uS;
-    const int gsel = 2 * bsel + (nsel ? 1 : 0);
-    const double base = nsel ? N0 : base_b, ys = nsel ? y_b * tlo.y : y_b;
-    const uint32_t nibs = nsel ? (bv >> 4) : (bv & 15u);
-    const int cmax = nsel ? c_hi : c_lo;
-    const double P1 = __builtin_fma(ys, t4s(T4, 1, nibs), base), P2 = __builtin_fma(ys, t4s(T4, 2, nibs), base);
-    const double P3 = __builtin_fma(ys, t4s(T4, 3, nibs), base), P4 = __builtin_fma(ys, t4s(T4, 4, nibs), base);
-    const int nc = ((cmax > 1 && P1 < uS) ? 1 : 0) + ((cmax > 2 && P2 < uS) ? 1 : 0) + ((cmax > 3 && P3 < uS) ? 1 : 0);
-    const double Ph = (nc == 0) ? P1 : (nc == 1) ? P2 : (nc == 2) ? P3 : P4;
-    const double Pp = (nc == 0) ? base : (nc == 1) ? P1 : (nc == 2) ? P2 : P3;
-    const int w = w0 + 4 * gsel + nc;
-    const double t = u - Ph * inv, tprev = u - Pp * inv;
-    const double e = 2.0 * REL * fmin(Ph, St - Ph) * inv + ABS;
-    const double eprev = 2.0 * REL * fmin(Pp, St - Pp) * inv + ABS;
-    const bool prev_ok = (w == 0) || (tprev > eprev);
-    const bool here_ok = (w == L) || (t < -e);
-#ifndef SR_FORCE_EXACT
-    if (prev_ok && here_ok) {
-      res = w;
-      POp = Oj + __popc(ww & ((1u << (w & 31)) - 1u));
-    }
-#else
-    (void)prev_ok; (void)here_ok; (void)w; (void)Oj;
-#endif
-  }
-  if (res < 0) {
-    if (h == 0) atomicAdd((unsigned long long *)fbk, 1ull);   /* exact-walk fallbacks (counted once per taxon) */
-    res = draw_exact(Pm, M, N, rev, o, L, u, K, tb);
-    POp = walk_prefix(Pm, M, N, NW, rev, res);
-  }
-  if (res == o) { dt0 = df0 = dt1 = df1 = 0; }
-  else if (res < o) { int O = POo - POp; int Z = (o - res) - O; dt0 = -Z; df0 = Z; dt1 = O; df1 = -O; }
-  else { int O = POp - POo; int Z = (res - o) - O; dt0 = Z; df0 = -Z; dt1 = -O; df1 = O; }
-  return res;
-}
-
 /* the forward walk words of column m (positions), NW <= NWM */
 template <int NWM>
 __device__ __forceinline__ void load_fwd(const uint32_t *Pm, int M, int NW, uint32_t (&fw)[NWM])
@@ -2168,14 +1942,12 @@ __device__ __forceinline__ void taxon_dt(int kind, const Prop &q, int a, int b, 
 /* The exact delta of one proposal: the reference's per-taxon terms (qval, mcmc.c:1214,
  * 1435, 1630 term order) compacted per 64-taxon chunk into cb, then summed sequentially in
  * ascending m by lane 0 of every wave.  Block-uniform call (contains a barrier). */
-/* PR (pair kernels): taxon m = m0 + lane / 2 is evaluated by its even lane; a wave's 32 taxa form
- * one chunk (ballot bits of even lanes in ascending lane order = ascending m).  KT = chunks. */
 /* GM: terms in HBM (exact_sum_gm).  SP (split chains): this half evaluates its own taxa [olo, ohi)
  * (whole chunks), the terms and counts go through the exchange (xsync: both halves' writes done),
  * and both halves compute the same sum. */
 /* kv (manycd sessions, MCD kernels): per-taxon c, d ([2M]) and cc, dd ([2M]) replace K's shared ones in
  * each taxon's term (mcmc.c:1212-1214 reads c, d per taxon) */
-template <bool PR, bool GM, bool SP, typename XSync>
+template <bool GM, bool SP, typename XSync>
 __device__ __forceinline__ double sr_exact_delta(int kind, Prop q, CD K, const int32_t *sab, const uint32_t *P, const uint16_t *pre,
                                               int M, int N, int KT, int olo, int ohi,
                                               int hl, int nh, const int16_t *hcnt, const int16_t *nhall, const uint32_t *hbx,
@@ -2183,17 +1955,16 @@ __device__ __forceinline__ double sr_exact_delta(int kind, Prop q, CD K, const i
                                               int lane, int wave, int TB, XSync &&xsync, const double *kv = nullptr,
                                               const double *kx = nullptr, int PS = 0)
 {
-  constexpr int CH = PR ? 32 : 64;
-  const bool ev = PR ? (lane & 1) == 0 : true;
-  for (int m0 = olo + wave * CH; m0 < ohi; m0 += (PR ? TB / 2 : TB)) {   /* (chunk starts below M: KT chunks) */
-    const int ch = m0 / CH, m = m0 + (PR ? (lane >> 1) : lane);
+  constexpr int CH = sr_chunk();
+  for (int m0 = olo + wave * CH; m0 < ohi; m0 += TB) {   /* (chunk starts below M: KT chunks) */
+    const int ch = m0 / CH, m = m0 + lane;
     int dt0 = 0, dt1 = 0;
-    if (m < M && ev)
+    if (m < M)
       taxon_dt(kind, q, sab[m], sab[M + m], P + m, pre + m, M, kind == PK_PI3 ? hard_bits_col<uint64_t>(P + m, M, hl, nh) : 0ull,
                hcnt, nhall, dt0, dt1, hbx, PS);
     CD Km = K;
     if (kv && m < M) { Km.c = kv[m]; Km.d = kv[M + m]; Km.cc = kx[m]; Km.dd = kx[M + m]; }
-    const double tv = (m < M && ev) ? qval(dt0, -dt0, dt1, -dt1, Km) : 0.0;
+    const double tv = (m < M) ? qval(dt0, -dt0, dt1, -dt1, Km) : 0.0;
     const uint64_t msk = __ballot(tv != 0.0);
     const int pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(msk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)msk, 0u));
     if (tv != 0.0) { if constexpr (SP) xst(cb + ch * CH + pos, tv); else cb[ch * CH + pos] = tv; }
@@ -2228,13 +1999,12 @@ __device__ __forceinline__ double sr_exact_delta(int kind, Prop q, CD K, const i
  * and sequential sum stay within (K + 7) 2^-53 B of S, K = #nonzero terms <= Knz = Y0 + Y1, so Eb = (Knz + 16)
  * 2^-52 B decides delta >= 0 and delta > log u whenever the true value is farther than Eb.  log u is first taken
  * in f32 (error << 2^-16 (1 + |log u|)), exactly only when that is too close.  The lane-parallel part: returns
- * cls 0 rejected, 1 accepted, 2 needs the exact delta or the exact log (pr: the pair kernels' packed Y). */
-__device__ __forceinline__ int pc_classify(int X0, int X1, int Y0, int Y1, const CD &K, double aC, double aD, bool pr,
+ * cls 0 rejected, 1 accepted, 2 needs the exact delta or the exact log. */
+__device__ __forceinline__ int pc_classify(int X0, int X1, int Y0, int Y1, const CD &K, double aC, double aD,
                                            uint32_t uw, double &Sp, double &Ebp, int &Knz)
 {
   Sp = ((double)X0 * K.cc - (double)X0 * K.d) + ((double)X1 * K.dd - (double)X1 * K.c);
-  /* PR: o[2] holds Y0 + Y1 (one packed field), o[3] = 0 -- bounded by the larger coefficient */
-  const double B = pr ? (double)(Y0 + Y1) * fmax(aC, aD) : (double)Y0 * aC + (double)Y1 * aD;
+  const double B = (double)Y0 * aC + (double)Y1 * aD;
   Knz = Y0 + Y1;   /* >= the number of nonzero terms: each has |dt0| + |dt1| >= 1 */
   Ebp = ((double)Knz + 16.0) * 0x1p-52 * B * SR_CERT_SCALE;
   if (Knz == 0 || Sp > Ebp) return 1;
@@ -2266,20 +2036,16 @@ __device__ __forceinline__ bool pc_resolve(double S, double Eb, int c0, int kz, 
   return false;
 }
 
-template <int TB, int NWM, bool GM, bool PR = false, bool SP = false, bool MCD = false, bool LPRE = false>
+template <int TB, int NWM, bool GM, bool SP = false, bool MCD = false, bool LPRE = false>
 __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
 {
-  static_assert(!SP || (GM && !PR && NWM == 0), "split chains: HBM-column kernels only");
-  static_assert(!MCD || (!PR && !SP && NWM == 0), "manycd: generic one-workgroup kernels only");
+  static_assert(!SP || (GM && NWM == 0), "split chains: HBM-column kernels only");
+  static_assert(!MCD || (!SP && NWM == 0), "manycd: generic one-workgroup kernels only");
   static_assert(!LPRE || SP, "column prefixes in LDS beside HBM columns: split chains only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NWV = TB / 64;
   /* wave: scalar in the HBM-column kernels (readfirstlane), so their per-wave LDS pointers live in SGPRs */
   const int tid = threadIdx.x, lane = tid & 63, wave = GM ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
-  /* PR (pair kernels): lanes 2t, 2t+1 own taxon t (tx) together, hf = which half of the pair;
-     otherwise one thread per taxon */
-  const int tx = PR ? (tid >> 1) : tid;   /* (hf: per sweep, below) */
-  constexpr int TXS = PR ? TB / 2 : TB;   /* taxon stride */
   /* SP: two workgroups per chain (sr_sp_half); both hold the whole block-uniform state (RNG ring,
      rpi, hard tables, c, d, loglik) and take every decision identically, each from sums exchanged
      with the other half; each owns half of the taxa (one per thread) */
@@ -2289,12 +2055,12 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   const int N = SR_FN > 0 ? SR_FN : A.N, M = SR_FM > 0 ? SR_FM : A.M;
   const int NW = SR_FN > 0 ? (SR_FN + 31) / 32 : A.NW, nh = SR_FH >= 0 ? SR_FH : A.nh;
   const int olo = SP ? half * sr_sp_half(M) : 0, ohi = SP ? min(M, olo + sr_sp_half(M)) : M;   /* own taxa */
-  const int mt = olo + tx;   /* own taxon, one-taxon-per-thread kernels */
-  const int KTC = (M + sr_chunk(PR) - 1) / sr_chunk(PR);   /* exact-delta chunks */
+  const int mt = olo + tid;   /* own taxon, one-taxon-per-thread kernels */
+  const int KTC = (M + sr_chunk() - 1) / sr_chunk();   /* exact-delta chunks */
   /* LPRE (split kernels whose LDS layout has room): the own half's column prefix table in LDS instead of HBM scratch
      -- the prefixes are read several times per proposal and taxon (config 5: 4.208 -> 4.151 ms per launch) */
   const int PS = LPRE ? sr_sp_half(M) : M;          /* the prefix table's stride */
-  const Lay L = sr_layout(N, M, NW, TB, GM, PR, nh, LPRE);
+  const Lay L = sr_layout(N, M, NW, TB, GM, nh, LPRE);
   double *tabs = (double *)(smem + L.tab);
   /* GM: the per-taxon arrays are the chain's HBM state itself (P, a/b, counts: updated in
      place) or its HBM scratch; otherwise LDS copies loaded here and stored at the end */
@@ -2317,9 +2083,9 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   int *hp = (int *)(smem + L.hpw) + wave * NHC;   /* this wave's copy of the hard positions */
   uint32_t *hbw = (uint32_t *)(smem + L.hbw) + wave * NW;   /* this wave's hard bitmap */
   const uint32_t *hbx = nh > SR_NHMAX ? hbw : nullptr;   /* many hard sites: hard ones from the bitmap */
-  double *T4w = (double *)(smem + L.t4) + ((PR || GM) ? 0 : wave) * T4STRIDE;   /* this wave's (PR, GM: the block's) 4-step tables */
-  constexpr bool SH8 = PR || GM;   /* one shared copy of the 8-step tables (built by waves 0-3, then a barrier) */
-  double *T8w = (double *)(smem + L.t8) + (SH8 ? 0 : wave) * T8STRIDE;   /* this wave's (SH8: the block's) 8-step tables */
+  double *T4w = (double *)(smem + L.t4) + (GM ? 0 : wave) * T4STRIDE;   /* this wave's (GM: the block's) 4-step tables */
+  /* this wave's 8-step tables (GM: the block's one shared copy, built by waves 0-3, then a barrier) */
+  double *T8w = (double *)(smem + L.t8) + (GM ? 0 : wave) * T8STRIDE;
   int *part = (int *)(smem + L.part);
   int *tot = (int *)(smem + L.tot);
   double *xs = (double *)(smem + L.xs) + wave;
@@ -2413,7 +2179,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   for (int m = olo + tid; m < ohi; m += TB) col_pre_build(pre + m, P + m, M, NW, PS);   /* own columns */
   {
     const int hl0 = (lane < nh) ? hp[lane] : 0;   /* loaded with every lane active */
-    if ((SP || M <= TXS) && mt < ohi) hbc = hard_bits_col<HM>(P + mt, M, hl0, nh);
+    if ((SP || M <= TB) && mt < ohi) hbc = hard_bits_col<HM>(P + mt, M, hl0, nh);
   }
   const double ec = sr_exp_m(SR_LOGEPSILON, &tb);
   const uint32_t nhard = (uint32_t)nh;
@@ -2432,10 +2198,9 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       if constexpr (GM) __asm__ volatile("" : "+v"(tid_sw));
       {
       const int tid = tid_sw, lane = tid & 63;
-      const int hf = PR ? (tid & 1) : 0, tx = PR ? (tid >> 1) : tid;
-      const int mt = olo + tx;
+      const int mt = olo + tid;
       const int ckslot = SP ? half * TB + tid : tid;   /* this thread's Gibbs checkpoint slots */
-      (void)hf; (void)mt; (void)ckslot;
+      (void)mt; (void)ckslot;
       const bool want_logl = (sw == A.spc - 1);
       /* this sweep's lane-parallel proposal tables, filled cooperatively (one entry per thread) before the
          phase-A barrier, at the stream position phase C most likely starts from: the c, d draws' fast path
@@ -2454,11 +2219,6 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           const int savail = min((int)((R.gen - tblk) * SR_MT_N - toff), 128);
           for (int k = tid; k < 4 * 128; k += TB)
             ptab_fill(ptab, ring, sbase, savail, k & 127, k >> 7, N, nh, hcnt, nhall, mdN, mdN1, md2, mdH, mdH1);
-          if (SR_DOUBLE == 7) {   /* (the same entries again) */
-            const int z = sr_opaque_zero();
-            for (int k = tid; k < 4 * 128; k += TB)
-              ptab_fill(ptab, ring, sbase, savail + z, (k & 127) + z, k >> 7, N, nh, hcnt, nhall, mdN, mdN1, md2, mdH, mdH1);
-          }
           tvalid = true;
         }
       }
@@ -2475,7 +2235,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       FST(11);
       /* one more ring block, published by the phase-A barrier: since the end-of-sweep barrier every wave read the ring
          from the sweep's cursor on (the proposal tables above; rng_ensure's own refills end with a barrier) */
-      if constexpr (!GM && !PR && !MCD) rng_topup<TB>(R, 0u, tid);
+      if constexpr (!GM && !MCD) rng_topup<TB>(R, 0u, tid);
       SR_SYNC();
       FST(11);
       {
@@ -2511,13 +2271,6 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           c = cv[0];
           d = cv[M];
           if (tid == 0) { misc[MS_ACC + 0] += M - 1; misc[MS_ACC + 1] += M - 1; }   /* samplec returns M (mcmc.c:785) */
-        } else if (SR_DOUBLE == 4 && [&] {   /* (diagnostic: the fast draw once more on a copy of the cursor) */
-                     DRng R2 = R;
-                     double c2 = c, d2 = d;
-                     const int z = sr_opaque_zero();
-                     const bool ok2 = draw_cd_fast(R2, c2, d2, s3 + z, s0, s1, s2, tb, lane);
-                     c += (ok2 ? c2 : 1.0) * (double)z; d += d2 * (double)z;
-                     return false; }()) {
         } else if (!draw_cd_fast(R, c, d, s3, s0, s1, s2, tb, lane)) {
           if (tid == 0) misc[MS_CDSEQ]++;
           double cd2[2] = {c, d};
@@ -2540,25 +2293,8 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       const double vA = (K.d - K.cc) * 1.4426950408889634;
       const double vB = (K.dd - K.c) * 1.4426950408889634;
       const double r2 = sr_exp_m(oddl ? K.c - K.dd : K.cc - K.d, &tb);
-      double rA = readlane_f64(r2, 0), rB = readlane_f64(r2, 1);   /* 2^-vA, 2^-vB */
-      if (SR_DOUBLE == 5) {   /* (diagnostic: K's logs and exps and the step tables once more) */
-        const double z = (double)sr_opaque_zero();
-        const double l1b = sr_log_m(1. - sr_exp_m((oddl ? d : c) + z, &tb), &tb);
-        const double r2b = sr_exp_m((oddl ? K.c - K.dd : K.cc - K.d) + z + l1b * z, &tb);
-        rA += readlane_f64(r2b, 0) * z; rB += readlane_f64(r2b, 1) * z;
-        if constexpr (NWM > 0 && !SH8) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int e = lane + 64 * q;
-            double pr = 1.0, sm = 0.0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { sm = sm + pr; pr = pr * (((e >> k) & 1) ? rB : rA); }
-            *reinterpret_cast<double2 *>(T8w + 2 * e) = make_double2(sm, pr);
-          }
-        }
-      }
-      /* PR: one shared copy of the tables, built by waves 0-4 (T8 quarters, T4), then a barrier */
-      if ((PR ? wave == 4 : (!GM || wave == NWV - 1)) && lane < 16) {   /* per-wave (PR, GM: shared) tables for 4 walk entries with bits = lane */
+      const double rA = readlane_f64(r2, 0), rB = readlane_f64(r2, 1);   /* 2^-vA, 2^-vB */
+      if ((!GM || wave == NWV - 1) && lane < 16) {   /* per-wave (GM: shared) tables for 4 walk entries with bits = lane */
         double sc[5];
         const double pr = t4_row(lane, rA, rB, sc);
 #pragma unroll
@@ -2567,14 +2303,14 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       if constexpr (NWM > 0 || GM) {   /* tables for 8 walk entries with bits = e: {sum of the 8 prefix products,
                                           product of all 8}; per wave 4 entries per lane, shared 1 per lane */
 #pragma unroll
-        for (int q = 0; q < (SH8 ? 1 : 4); ++q) {
-          const int e = lane + 64 * (SH8 ? wave : q);
+        for (int q = 0; q < (GM ? 1 : 4); ++q) {
+          const int e = lane + 64 * (GM ? wave : q);
           const double2 te = t8_entry(e, rA, rB);
-          if (!SH8 || wave < 4) *reinterpret_cast<double2 *>(T8w + 2 * e) = te;
+          if (!GM || wave < 4) *reinterpret_cast<double2 *>(T8w + 2 * e) = te;
         }
-        if (lane == 0 && (!SH8 || wave == (PR ? 4 : 0))) *reinterpret_cast<double2 *>(T8w + 2 * 256) = make_double2(0.0, 1.0);
+        if (lane == 0 && (!GM || wave == 0)) *reinterpret_cast<double2 *>(T8w + 2 * 256) = make_double2(0.0, 1.0);
       }
-      if constexpr (SH8) SR_SYNC(); else wsync();
+      if constexpr (GM) SR_SYNC(); else wsync();
 
 #ifdef SR_STAMP_GIBBS
       STAMP(5);
@@ -2587,7 +2323,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
          For phase B only: raised for the whole kernel it is slower than no priority at all (+1.5 %), and kept up to
          the batch barrier +3.9 % against this form (profiles/r07b_ab_prio_readlane.json, r07c_ab_final.json).
          (s_setprio ignores EXEC: the condition is a scalar.) */
-      if constexpr (!GM && !PR && TB == 512) {
+      if constexpr (!GM && TB == 512) {
         if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= TB / 2) __builtin_amdgcn_s_setprio(1);
       }
       /* ============ phase B: Gibbs update of own (a_m, b_m) (mcmc_sampleab) */
@@ -2604,7 +2340,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
         FST(1);
         rng_ensure(R, min(2 * (mhi - mlo) + SR_RNG_SLACK, rcap), tid, TB);
         FST(8);
-        for (int m = max(mlo, olo) + tx; m < min(mhi, ohi); m += TXS) {   /* PR: pair-uniform; SP: own taxa */
+        for (int m = max(mlo, olo) + tid; m < min(mhi, ohi); m += TB) {   /* SP: own taxa */
           const uint32_t *Pm = P + m;
           const double ua = rng_peek(R, 2 * (m - mlo)) / 4294967296.0;
           const double ub = rng_peek(R, 2 * (m - mlo) + 1) / 4294967296.0;
@@ -2613,25 +2349,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           /* a_m over [0, b_m], then b_m over the reversed column with limit N - a_new: one
              inlined copy of the draw, two trips */
           int na = a0, nb = b0;
-          if constexpr (PR) {   /* pair kernels: each lane of the pair walks half of the words */
-            const uint16_t *prem = pre + m;
-            const int POa = col_pre(prem, Pm, M, a0, PS);
-            const int POb = (int)prem[NW * PS] - col_pre(prem, Pm, M, b0, PS);
-            uint32_t wk[5];
-            int d0, e0, d1, e1;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) { const int k = 5 * hf + i; wk[i] = (k < NW) ? Pm[min(k, NW - 1) * M] : 0u; }
-            na = draw_pair9(wk, hf, Pm, M, N, NW, false, a0, b0, POa, ua, K, tb, vA, vB, T4w, T8w, &misc[MS_FBK], d0, e0, d1, e1);
-            t0 += d0; f0 += e0; t1 += d1; f1 += e1;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-              const int k = 5 * hf + i;
-              wk[i] = (k < NW) ? walk_word(Pm, M, N, NW, true, min(k, NW - 1)) : 0u;
-            }
-            nb = N - draw_pair9(wk, hf, Pm, M, N, NW, true, N - b0, N - na, POb, ub, K, tb, vA, vB, T4w, T8w, &misc[MS_FBK],
-                                d0, e0, d1, e1);
-            t0 += d0; f0 += e0; t1 += d1; f1 += e1;
-          } else if constexpr (MCD) {   /* manycd: the taxon's own coefficients, the exact reference walk */
+          if constexpr (MCD) {   /* manycd: the taxon's own coefficients, the exact reference walk */
             const uint16_t *prem = pre + m;
             const int POa = col_pre(prem, Pm, M, a0, PS);
             const int POb = (int)prem[NW * PS] - col_pre(prem, Pm, M, b0, PS);
@@ -2663,15 +2381,8 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
 #pragma unroll
                 for (int k = 0; k < NWM; ++k) wk[k] = rw[k];
               }
-              int res = draw_fast_s<NWM>(wk, Pm, M, N, rev, rev ? N - b0 : a0, rev ? N - na : b0, rev ? POb : POa,
+              const int res = draw_fast_s<NWM>(wk, Pm, M, N, rev, rev ? N - b0 : a0, rev ? N - na : b0, rev ? POb : POa,
                                          rev ? ub : ua, K, tb, vA, vB, T4w, T8w, &misc[MS_FBK], d0, e0, d1, e1);
-              if (SR_DOUBLE == 3) {
-                const int z = sr_opaque_zero();
-                int q0, q1, q2, q3;
-                const int r2 = draw_fast_s<NWM>(wk, Pm, M, N, rev, (rev ? N - b0 : a0) + z, rev ? N - na : b0, rev ? POb : POa,
-                                                (rev ? ub : ua) + (double)z, K, tb, vA, vB, T4w, T8w, &misc[MS_FBK], q0, q1, q2, q3);
-                res |= r2 & z; d0 |= q0 & z; e0 |= q1 & z; d1 |= q2 & z; e1 |= q3 & z;
-              }
               t0 += d0; f0 += e0; t1 += d1; f1 += e1;
               if (rev) nb = N - res; else na = res;
             }
@@ -2690,16 +2401,14 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
             if (rev) nb = N - res; else na = res;
           }
           }
-          if (!PR || hf == 0) {   /* PR: the even lane writes the pair's results */
-            nchg += (na != a0) + (nb != b0);
-            sab[m] = na; sab[M + m] = nb;
-            scnt[m] = t0; scnt[M + m] = f0; scnt[2 * M + m] = t1; scnt[3 * M + m] = f1;
-            if (want_logl) {   /* mcmc_logl term (mcmc.c:643-644); manycd: the taxon's c, d (mcmc.c:641-642) */
-              const double kcc = MCD ? cx[m] : K.cc, kd = MCD ? cv[M + m] : K.d, kdd = MCD ? cx[M + m] : K.dd,
-                           kc = MCD ? cv[m] : K.c;
-              const double lt = (double)t0 * kcc + (double)f0 * kd + (double)t1 * kdd + (double)f1 * kc;
-              if constexpr (SP) xst(lbuf + m, lt); else lbuf[m] = lt;
-            }
+          nchg += (na != a0) + (nb != b0);
+          sab[m] = na; sab[M + m] = nb;
+          scnt[m] = t0; scnt[M + m] = f0; scnt[2 * M + m] = t1; scnt[3 * M + m] = f1;
+          if (want_logl) {   /* mcmc_logl term (mcmc.c:643-644); manycd: the taxon's c, d (mcmc.c:641-642) */
+            const double kcc = MCD ? cx[m] : K.cc, kd = MCD ? cv[M + m] : K.d, kdd = MCD ? cx[M + m] : K.dd,
+                         kc = MCD ? cv[m] : K.c;
+            const double lt = (double)t0 * kcc + (double)f0 * kd + (double)t1 * kdd + (double)f1 * kc;
+            if constexpr (SP) xst(lbuf + m, lt); else lbuf[m] = lt;
           }
         }
         rng_skip(R, 2 * (mhi - mlo));
@@ -2707,7 +2416,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
         const int nw = wave_sum_i32((int)nchg);
         if (lane == 0 && nw) atomicAdd((unsigned long long *)&misc[MS_CAB], (unsigned long long)nw);
       }
-      if constexpr (!GM && !PR && TB == 512) {   /* ... and back */
+      if constexpr (!GM && TB == 512) {   /* ... and back */
         if (__builtin_amdgcn_readfirstlane((int)threadIdx.x) >= TB / 2) __builtin_amdgcn_s_setprio(0);
       }
       FST(1);
@@ -2992,12 +2701,12 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           const bool pack = N < 512;   /* one taxon per thread: per-wave sums fit 16-bit fields */
           /* own taxon's limits and hard-site bits, fixed for the batch (one taxon per thread) */
           /* register-walk kernels: M <= TB (sr_regwalk); 1024-thread split halves hold <= TB taxa (compile-time) */
-          const bool one = NWM > 0 || (SP && TB == 1024) || (SP && ohi - olo <= TB) || M <= TXS;
+          const bool one = NWM > 0 || (SP && TB == 1024) || (SP && ohi - olo <= TB) || M <= TB;
           int a1 = 0, b1 = 0;
           const HM hb1 = hbc;
           /* every thread owns a taxon when the shape is compiled in and fills the block (the bench kernel): the
              ownership test is then a constant, not an exec mask re-set around every slot */
-          constexpr bool ALLOWN = !SP && !PR && SR_FM > 0 && SR_FM >= TB;
+          constexpr bool ALLOWN = !SP && SR_FM > 0 && SR_FM >= TB;
           const bool own = ALLOWN || mt < ohi;
           if (one && own) { a1 = sab[mt]; b1 = sab[M + mt]; }
           FST(13);
@@ -3008,52 +2717,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
 #else
           STAMP(3);
 #endif
-          if constexpr (PR) {
-            /* pair kernels: the proposals in slot pairs of one code path (kinds pi1, pi2 / swap,
-               pi3); the even lane of a taxon evaluates the pair's first proposal, the odd lane the
-               second, and the per-wave sums are kept per lane parity (the two proposals' sums) */
-            constexpr int SPA[9] = {1, 2, 3, 7, 8, 9, 13, 14, 15};
-            constexpr int SPB[9] = {4, 5, 6, 10, 11, 12, -1, 0, -1};
-            constexpr uint64_t EV = 0x5555555555555555ull, OD = 0xAAAAAAAAAAAAAAAAull;
-#pragma unroll
-            for (int sp = 0; sp < 9; ++sp) {   /* terms and their sums per slot pair (no per-slot arrays:
-                                                  the register budget is 128 at four waves per SIMD) */
-              const int pa = SPA[sp], pb = SPB[sp];
-              const bool va = pa >= p0 && pa < pend && !vetoed(pa);
-              const bool vb = pb >= 0 && pb >= p0 && pb < pend && !vetoed(pb >= 0 ? pb : 0);
-              if (va || vb) {
-                const Prop qa = load_prop(pa), qb = load_prop(pb >= 0 ? pb : pa);
-                Prop q;
-                q.i = hf ? qb.i : qa.i; q.j = hf ? qb.j : qa.j; q.ii = hf ? qb.ii : qa.ii; q.jj = hf ? qb.jj : qa.jj;
-                q.inc1 = hf ? qb.inc1 : qa.inc1; q.inc2 = hf ? qb.inc2 : qa.inc2;
-                q.Kn = hf ? qb.Kn : qa.Kn; q.r0 = hf ? qb.r0 : qa.r0;
-                int d0 = 0, d1 = 0;
-                if ((hf ? vb : va) && tx < M)
-                  taxon_dt(prop_kind(pa), q, a1, b1, P + tx, pre + tx, M, hb1, hcnt, nhall, d0, d1, hbx, PS);
-                int Xa0, Xa1, Ya, Xb0, Xb1, Yb;
-                if (prop_kind(pa) == PK_PI1) {   /* dt in {-1, 0, 1}, dt0 dt1 = 0: ballot counts per parity */
-                  const uint64_t p0m = __ballot(d0 > 0), n0m = __ballot(d0 < 0);
-                  const uint64_t p1m = __ballot(d1 > 0), n1m = __ballot(d1 < 0);
-                  Xa0 = (int)__popcll(p0m & EV) - (int)__popcll(n0m & EV); Xb0 = (int)__popcll(p0m & OD) - (int)__popcll(n0m & OD);
-                  Xa1 = (int)__popcll(p1m & EV) - (int)__popcll(n1m & EV); Xb1 = (int)__popcll(p1m & OD) - (int)__popcll(n1m & OD);
-                  Ya = (int)(__popcll((p0m | n0m) & EV) + __popcll((p1m | n1m) & EV));
-                  Yb = (int)(__popcll((p0m | n0m) & OD) + __popcll((p1m | n1m) & OD));
-                } else {   /* 16-bit field per parity: 32 lanes x (dt + N) < 2^16 for N < 1024 */
-                  const int sh = 16 * hf;
-                  const uint32_t u0 = (uint32_t)wave_sum_i32((int)((uint32_t)(d0 + N) << sh));
-                  const uint32_t u1 = (uint32_t)wave_sum_i32((int)((uint32_t)(d1 + N) << sh));
-                  const uint32_t u2 = (uint32_t)wave_sum_i32((int)((uint32_t)(abs(d0) + abs(d1)) << sh));
-                  Xa0 = (int)(u0 & 0xffffu) - 32 * N; Xb0 = (int)(u0 >> 16) - 32 * N;
-                  Xa1 = (int)(u1 & 0xffffu) - 32 * N; Xb1 = (int)(u1 >> 16) - 32 * N;
-                  Ya = (int)(u2 & 0xffffu); Yb = (int)(u2 >> 16);
-                }
-                if (lane == 0 && va) { int *o = pw + (pa * NWV + wave) * 8; o[0] = Xa0; o[1] = Xa1; o[2] = Ya; o[3] = 0; }
-                if (lane == 1 && vb) { int *o = pw + (pb * NWV + wave) * 8; o[0] = Xb0; o[1] = Xb1; o[2] = Yb; o[3] = 0; }
-              }
-            }
-            FST(3);
-            STAMP_K(PK_PI3);
-          } else if (one) {
+          if (one) {
             /* one taxon per thread: all 16 proposal slots unrolled; slot s has the compile-time
                kind prop_kind(s), so each copy holds one kind's code and the slots' loads, ALU
                and reductions are independent */
@@ -3068,18 +2732,6 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                 d0s[sI] = dt0; d1s[sI] = dt1;
               }
             }
-            if (SR_DOUBLE == 1) {
-              const int z = sr_opaque_zero();
-#pragma unroll
-              for (int sI = 0; sI < 16; ++sI) {
-                if (sI >= p0 && sI < pend && !vetoed(sI)) {
-                  const Prop q = load_prop(sI);
-                  int dt0 = 0, dt1 = 0;
-                  if (mt < ohi) taxon_dt(prop_kind(sI), q, a1 + z, b1, P + mt, pre + mt, M, hb1, hcnt, nhall, dt0, dt1, hbx, PS);
-                  d0s[sI] |= dt0 & z; d1s[sI] |= dt1 & z;
-                }
-              }
-            }
             FST(3);
             if (SR_TSUMS && !GM && pack && pend - p0 >= SR_TSUMS) {   /* (GM: see below) */
               /* all 16 slots' sums of one wave in one transposed reduction (wave_sum32_t): values 0-15 the packed
@@ -3092,16 +2744,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                 u[sI] = (uint32_t)(d0s[sI] + N) | ((uint32_t)(d1s[sI] + N) << 16);
                 u[16 + sI] = (uint32_t)((d0s[sI] | d1s[sI]) != 0) | ((uint32_t)(d0s[sI] != 0) << 16);
               }
-              uint32_t v = wave_sum32_t(u, lane);
-              if (SR_DOUBLE == 2) {
-                const uint32_t z = (uint32_t)sr_opaque_zero();
-#pragma unroll
-                for (int sI = 0; sI < 16; ++sI) {
-                  u[sI] = (uint32_t)(d0s[sI] + N) | ((uint32_t)(d1s[sI] + N) << 16) | z;
-                  u[16 + sI] = ((uint32_t)((d0s[sI] | d1s[sI]) != 0) | ((uint32_t)(d0s[sI] != 0) << 16)) + z;
-                }
-                v |= wave_sum32_t(u, lane) & z;
-              }
+              const uint32_t v = wave_sum32_t(u, lane);
               const int sl = (((lane >> 1) & 1) << 3) | (((lane >> 2) & 1) << 2) | (((lane >> 3) & 1) << 1) | ((lane >> 4) & 1);
               const uint32_t pk = (uint32_t)__builtin_amdgcn_ds_bpermute(sl << 2, vpk);   /* slot sl's record */
               if (lane < 32) {
@@ -3207,7 +2850,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           /* one more ring block, published by the batch barrier: since the batch barrier before this one every wave
              read the ring from this batch's cursor on.  Not in the sweep's first batch: a wave may still be reading its
              c, d and Gibbs words, which start a variable distance below (the sequential c, d draws). */
-          if constexpr (!GM && !PR && !MCD) { if (p0 > 0) rng_topup<TB>(R, 0u, tid); }
+          if constexpr (!GM && !MCD) { if (p0 > 0) rng_topup<TB>(R, 0u, tid); }
           SR_SYNC();
           if constexpr (SP) {   /* this half's sums of the batch's proposals (lane p of wave 0), exchanged */
             if (wave == 0 && lane >= p0 && lane < pend && lane < 16 && !((vpk >> 26) & 1)) {
@@ -3245,7 +2888,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                   X0 += xld(yp); X1 += xld(yp + 1); Y0 += xld(yp + 2); Y1 += xld(yp + 3);
                 }
                 uwp = (uint32_t)vuw;
-                cls = pc_classify(X0, X1, Y0, Y1, K, aC, aD, PR, uwp, Sp, Ebp, Knz);
+                cls = pc_classify(X0, X1, Y0, Y1, K, aC, aD, uwp, Sp, Ebp, Knz);
 #ifdef SR_FORCE_EXACT   /* test build: every decision by the exact sequential delta */
                 cls = (Knz == 0) ? 1 : 2;
                 Ebp = __builtin_inf();
@@ -3277,13 +2920,13 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
             const bool decided = pc_resolve(S, Eb, c0, kz, u, tb, accept, udrawn, have_exact, dl);
             if (!decided || (accept && want_logl && !have_exact)) {   /* the exact sequential delta */
               if constexpr (SP)
-                dl = sr_exact_delta<PR, GM, SP>(kind, q, K, sab, P, pre, M, N, KTC, olo, ohi, hl, nh, hcnt, nhall, hbx,
-                                                cbuf + xpar * KTC * sr_chunk(PR), xb + 272 + xpar * KTC, xs, lane, wave,
-                                                TB, xsync, nullptr, nullptr, PS);
+                dl = sr_exact_delta<GM, SP>(kind, q, K, sab, P, pre, M, N, KTC, olo, ohi, hl, nh, hcnt, nhall, hbx,
+                                            cbuf + xpar * KTC * sr_chunk(), xb + 272 + xpar * KTC, xs, lane, wave,
+                                            TB, xsync, nullptr, nullptr, PS);
               else   /* (no exchange: the one-workgroup kernels never see the split machinery) */
-                dl = sr_exact_delta<PR, GM, SP>(kind, q, K, sab, P, pre, M, N, KTC, 0, M, hl, nh, hcnt, nhall, hbx,
-                                                cbuf + xpar * KTC * sr_chunk(PR), ccnt + xpar * KTC, xs, lane, wave, TB,
-                                                [] {}, cv, cx);
+                dl = sr_exact_delta<GM, SP>(kind, q, K, sab, P, pre, M, N, KTC, 0, M, hl, nh, hcnt, nhall, hbx,
+                                            cbuf + xpar * KTC * sr_chunk(), ccnt + xpar * KTC, xs, lane, wave, TB,
+                                            [] {}, cv, cx);
               xpar ^= 1;
               if (!decided) {
                 if (tid == 0) misc[MS_NEXACT]++;
@@ -3318,7 +2961,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
           if (tid == 0) misc[MS_ACC + (kind == PK_PI1 ? 3 : kind == PK_PI2 ? 4 : kind == PK_SWAP ? 5 : 6)]++;
           loglik += delta;
           const int16_t *nhp = nhall + q.r0;   /* pi3: the non-hard positions of [i, j] in order */
-          for (int m = (PR && hf) ? M : olo + tx; m < ohi; m += TXS) {   /* PR: the even lane of each pair; SP: own taxa */
+          for (int m = olo + tid; m < ohi; m += TB) {   /* SP: own taxa */
             uint32_t *Pm = P + m;
             uint16_t *prem = pre + m;
             const int a = sab[m], b = sab[M + m];
@@ -3500,7 +3143,6 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
             if constexpr (GM) SR_SYNC(); else wsync();   /* GM: every wave is past its reads of the shared tables */
             build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane, !GM || wave == 0);
             if constexpr (GM) SR_SYNC();                  /* ... and the next batch reads the new ones */
-            if (SR_DOUBLE == 8 && !GM) { wsync(); build_hard_tables(hp, nh, N, NW, hbw, hcnt, nhall, lane); }
             tvalid = false;   /* (the proposal tables depend on the hard positions) */
           }
           FST(9);
@@ -3512,7 +3154,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       FST(0);
       /* ... and one published by the end-of-sweep barrier: since the last batch barrier no wave read the ring at all
          (decisions and moves), and the cursor moved by that batch's words (at most 128: `avail`) */
-      if constexpr (!GM && !PR && !MCD) rng_topup<TB>(R, 1u, tid);
+      if constexpr (!GM && !MCD) rng_topup<TB>(R, 1u, tid);
       SR_SYNC();
       FST(11);
       }
@@ -3605,7 +3247,7 @@ template __global__ void sr_sweep_kernel<SR_JIT_TB, SR_JIT_NWM, false>(KArgs);
 __constant__ unsigned long long sr_spec_abi[4] = {
     sizeof(KArgs), (unsigned long long)SR_JIT_TB | ((unsigned long long)SR_JIT_NWM << 16),
     (unsigned long long)SR_FN | ((unsigned long long)SR_FM << 16) | ((unsigned long long)(SR_FH & 0xffff) << 32),
-    (unsigned long long)sr_layout(SR_FN, SR_FM, (SR_FN + 31) / 32, SR_JIT_TB, false, false, SR_FH).total};
+    (unsigned long long)sr_layout(SR_FN, SR_FM, (SR_FN + 31) / 32, SR_JIT_TB, false, SR_FH).total};
 #else
 /* ================================================================ session layer */
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
@@ -3613,7 +3255,7 @@ __constant__ unsigned long long sr_spec_abi[4] = {
 
 
 struct srk_dev {
-  int device, N, M, NW, nh, nchains, TB, TPT, rec_cap, gm, pr, sp, grid, coop;
+  int device, N, M, NW, nh, nchains, TB, rec_cap, gm, sp, grid, coop;
   int lpre;                /* split kernels: the own half's column prefixes in LDS (LPRE kernels) */
   int mcd;                 /* manycd: per-taxon c, d (MCD kernels) */
   int jit;                 /* the launch uses the shape-specialised kernel (srk_spec_load) */
@@ -3635,36 +3277,20 @@ typedef void (*sr_kfn)(KArgs);
 
 /* NWM: walks of <= 9 / 17 words (N + 1 entries: N <= 287 / 543) use the register-resident
  * Gibbs draw, longer ones the LDS walk.  gm: the HBM-column variant (sr_layout) */
-/* the pair kernel (two lanes per taxon, 1024 threads): walks of <= 9 words (N <= 287) and 257..512
- * taxa with columns in LDS.  Opt-in (SR_KERNEL=pair in the environment): bit-exact, but 1.67x slower
- * than the one-thread-per-taxon kernel on the bench workload (profiles/r03c_ab_pair.json: 24.6 vs
- * 14.7 ms per launch) -- its per-wave instruction count fell only 13 % (4.3 k vs 5.0 k VALU per
- * wave per sweep: most of a wave's work is per proposal and per sweep, not per taxon, and all 16
- * waves repeat it), the 128-VGPR budget spills 171 registers, and waves park 60 % of their cycles
- * (r03d SQ passes). */
-static bool sr_pair_ok(int N, int M)
-{
-  const char *e = getenv("SR_KERNEL");
-  if (!e || strcmp(e, "pair") != 0) return false;
-  return sr_nwm(N) == 9 && M > 256 && M <= 512;
-}
-
-static sr_kfn sr_pick_kernel(int TB, int N, int M, bool gm, bool pr, int nh, bool sp = false, bool mcd = false,
-                             bool lpre = false)
+static sr_kfn sr_pick_kernel(int TB, int N, int M, bool gm, int nh, bool sp = false, bool mcd = false, bool lpre = false)
 {
   if (mcd) {   /* manycd: the generic one-workgroup kernels at 1024 threads */
-    if (TB != 1024 || pr || sp) return nullptr;
-    return gm ? (sr_kfn)sr_sweep_kernel<1024, 0, true, false, false, true>
-              : (sr_kfn)sr_sweep_kernel<1024, 0, false, false, false, true>;
+    if (TB != 1024 || sp) return nullptr;
+    return gm ? (sr_kfn)sr_sweep_kernel<1024, 0, true, false, true>
+              : (sr_kfn)sr_sweep_kernel<1024, 0, false, false, true>;
   }
-  if (pr) return (TB == 1024 && !gm) ? (sr_kfn)sr_sweep_kernel<1024, 9, false, true> : nullptr;
 #ifndef SR_STAMPS
   if (sp) {   /* lpre: the own half's column prefixes in LDS (where the layout fits them), else in HBM scratch */
     if (!gm) return nullptr;
-    if (TB == 1024) return lpre ? (sr_kfn)sr_sweep_kernel<1024, 0, true, false, true, false, true>
-                              : (sr_kfn)sr_sweep_kernel<1024, 0, true, false, true>;
-    if (TB == 512) return lpre ? (sr_kfn)sr_sweep_kernel<512, 0, true, false, true, false, true>
-                             : (sr_kfn)sr_sweep_kernel<512, 0, true, false, true>;
+    if (TB == 1024) return lpre ? (sr_kfn)sr_sweep_kernel<1024, 0, true, true, false, true>
+                              : (sr_kfn)sr_sweep_kernel<1024, 0, true, true>;
+    if (TB == 512) return lpre ? (sr_kfn)sr_sweep_kernel<512, 0, true, true, false, true>
+                             : (sr_kfn)sr_sweep_kernel<512, 0, true, true>;
     return nullptr;
   }
 #else
@@ -3684,9 +3310,9 @@ static sr_kfn sr_pick_kernel(int TB, int N, int M, bool gm, bool pr, int nh, boo
 }
 
 /* ---- the kernel a session runs ----------------------------------------------------------------
- * Block size, variant (LDS columns / HBM columns / pair kernel) and LDS bytes from the shape alone (no
+ * Block size, variant (LDS columns / HBM columns) and LDS bytes from the shape alone (no
  * HIP call): srk_create launches this plan, srk_plan / sr_specialize report it without a GPU. */
-struct srk_kplan { int TB, pr, gm, mcd; size_t lds; };
+struct srk_kplan { int TB, gm, mcd; size_t lds; };
 
 static int plan_kernel(int N, int M, int nh, int block_threads, int gm_force, int mcd, srk_kplan *kp)
 {
@@ -3697,37 +3323,33 @@ static int plan_kernel(int N, int M, int nh, int block_threads, int gm_force, in
     if (TB > 0 && TB != 1024) return -6;
     TB = 1024;
   }
-  /* the pair kernel where it was asked for (two lanes per taxon, 1024 threads), else one thread per
-     taxon in the smallest block of 256..1024 threads that covers M */
-  int pr = (TB <= 0 && !mcd && gm_force != 1 && nh <= 32 && sr_pair_ok(N, M)) ? 1 : 0;
-  if (pr) TB = 1024;
+  /* one thread per taxon in the smallest block of 256..1024 threads that covers M */
   if (TB <= 0) { TB = 256; while (TB < M && TB < 1024) TB *= 2; }
   /* columns in LDS when the whole layout fits, else the HBM-column variant */
   int gm = 0;
-  Lay L = sr_layout(N, M, NW, TB, false, pr != 0, nh);
-  if (L.total > 160 * 1024 && block_threads <= 0 && !mcd && !pr && gm_force != 1 && TB == 1024 && M <= 1024) {
+  Lay L = sr_layout(N, M, NW, TB, false, nh);
+  if (L.total > 160 * 1024 && block_threads <= 0 && !mcd && gm_force != 1 && TB == 1024 && M <= 1024) {
     /* mid-size shapes (513-1024 taxa, N up to ~320): the 1024-thread LDS layout does not fit, a 512-thread one (two
        taxa per thread) does -- LDS columns there beat HBM columns at 1024 threads by 11-30 % (256 x 600, 200 x 800,
        128 x 1000: profiles/r06c_ab_planner.json, same box, parity legs green) */
-    const Lay L2 = sr_layout(N, M, NW, 512, false, false, nh);
-    if (L2.total <= 160 * 1024 && sr_pick_kernel(512, N, M, false, false, nh, false, false)) { TB = 512; L = L2; }
+    const Lay L2 = sr_layout(N, M, NW, 512, false, nh);
+    if (L2.total <= 160 * 1024 && sr_pick_kernel(512, N, M, false, nh)) { TB = 512; L = L2; }
   }
-  if (L.total > 160 * 1024) { gm = 1; L = sr_layout(N, M, NW, TB, true, false, nh); }
+  if (L.total > 160 * 1024) { gm = 1; L = sr_layout(N, M, NW, TB, true, nh); }
   if (gm_force >= 0 && gm_force != gm) {   /* explicit variant request (tests) */
     gm = gm_force;
-    L = sr_layout(N, M, NW, TB, gm != 0, pr != 0, nh);
+    L = sr_layout(N, M, NW, TB, gm != 0, nh);
   }
-  if (gm) pr = 0;
-  if (!sr_pick_kernel(TB, N, M, gm != 0, pr != 0, nh, false, mcd != 0) || L.total > 160 * 1024) return -6;
-  kp->TB = TB; kp->pr = pr; kp->gm = gm; kp->mcd = mcd; kp->lds = L.total;
+  if (!sr_pick_kernel(TB, N, M, gm != 0, nh, false, mcd != 0) || L.total > 160 * 1024) return -6;
+  kp->TB = TB; kp->gm = gm; kp->mcd = mcd; kp->lds = L.total;
   return 0;
 }
 
-/* the specialised kernel's shape: LDS-column sessions of the one-thread-per-taxon kernels (the HBM-column
-   split kernel measured 4.4 % slower specialised, profiles/r03z6_ab_jit.json; the pair kernel is opt-in) */
+/* the specialised kernel's shape: LDS-column sessions of the one-workgroup kernels (the HBM-column split
+   kernel measured 4.4 % slower specialised, profiles/r03z6_ab_jit.json) */
 static bool spec_shape_of(int N, int M, int nh, const srk_kplan &kp, sr_spec_shape *s)
 {
-  if (kp.gm || kp.pr || kp.mcd) return false;
+  if (kp.gm || kp.mcd) return false;
   s->TB = kp.TB;
   s->NWM = sr_regwalk(N, M, kp.TB, false, nh) ? sr_nwm(N) : 0;
   s->N = N; s->M = M; s->NH = nh;
@@ -3792,7 +3414,7 @@ static int srk_spec_load(srk_dev *d, const srk_spec_src *src)
   const sr_spec_shape &s = src->s;
   char log[4700];
   char name[128];
-  snprintf(name, sizeof name, "_Z15sr_sweep_kernelILi%dELi%dELb0ELb0ELb0ELb0ELb0EEv5KArgs", s.TB, s.NWM);
+  snprintf(name, sizeof name, "_Z15sr_sweep_kernelILi%dELi%dELb0ELb0ELb0ELb0EEv5KArgs", s.TB, s.NWM);
   unsigned long long abi[4] = {0, 0, 0, 0};
   const unsigned long long want[4] = {
       sizeof(KArgs), (unsigned long long)s.TB | ((unsigned long long)s.NWM << 16),
@@ -3891,7 +3513,7 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
   srk_dev *d = new srk_dev();
   d->device = device; d->N = st->N; d->M = st->M; d->NW = st->NW; d->nh = st->nh; d->nchains = st->nchains;
   const int TB = kp.TB;
-  d->TB = TB; d->TPT = 1; d->pr = kp.pr; d->gm = kp.gm; d->mcd = kp.mcd; d->lds = kp.lds;
+  d->TB = TB; d->gm = kp.gm; d->mcd = kp.mcd; d->lds = kp.lds;
   /* split chains (two co-resident workgroups per chain, one taxon per thread): HBM columns at 1024
      threads when the taxa exceed one block but each half fits it, and the whole grid (16 blocks per
      8 chains) is co-resident -- launched cooperatively.  SR_SPLIT=0 disables it, SR_SPLIT=1 also
@@ -3903,10 +3525,10 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
     const int Mh = sr_sp_half(st->M);
     /* the split kernels' own layout: the own half's column prefixes in LDS where they fit (up to N ~ 1300 at 1024
        threads), else in HBM scratch (any N) */
-    const size_t lds_lpre = sr_layout(st->N, st->M, st->NW, TB, true, false, st->nh, true).total;
+    const size_t lds_lpre = sr_layout(st->N, st->M, st->NW, TB, true, st->nh, true).total;
     const bool lpre = lds_lpre <= 160 * 1024;
-    const size_t lds_sp = lpre ? lds_lpre : sr_layout(st->N, st->M, st->NW, TB, true, false, st->nh, false).total;
-    sr_kfn ks = sr_pick_kernel(TB, st->N, st->M, true, false, st->nh, true, false, lpre);
+    const size_t lds_sp = lpre ? lds_lpre : sr_layout(st->N, st->M, st->NW, TB, true, st->nh, false).total;
+    sr_kfn ks = sr_pick_kernel(TB, st->N, st->M, true, st->nh, true, false, lpre);
     if (lds_sp > 160 * 1024) ks = nullptr;
     /* SR_SPLIT=2 (experiment, opt-in only): 512-thread halves of up to two blocks' taxa, several taxa per
        thread (256 VGPRs, 8 waves per CU; measured slower) -- never chosen without it */
@@ -3968,7 +3590,7 @@ extern "C" int srk_create(const sr_state_host *st, int device, int block_threads
     rc |= dev_alloc_copy(d, &A.xerr, (const int *)nullptr, 1);
   }
   if (rc) { srk_destroy(d); return -5; }
-  sr_kfn k = sr_pick_kernel(TB, st->N, st->M, d->gm != 0, d->pr != 0, st->nh, d->sp != 0, d->mcd != 0, d->lpre != 0);
+  sr_kfn k = sr_pick_kernel(TB, st->N, st->M, d->gm != 0, st->nh, d->sp != 0, d->mcd != 0, d->lpre != 0);
   if (hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->lds) != hipSuccess) {
     srk_destroy(d);
     return -5;
@@ -3999,7 +3621,7 @@ extern "C" int srk_run(srk_dev *d, int calls, int spc, int save, int rec_base)
   HIPCHK(hipSetDevice(d->device));
   KArgs A = d->args;
   A.calls = calls; A.spc = spc; A.save = save; A.rec_base = rec_base;
-  sr_kfn k = sr_pick_kernel(d->TB, d->N, d->M, d->gm != 0, d->pr != 0, d->nh, d->sp != 0, d->mcd != 0, d->lpre != 0);
+  sr_kfn k = sr_pick_kernel(d->TB, d->N, d->M, d->gm != 0, d->nh, d->sp != 0, d->mcd != 0, d->lpre != 0);
   if (d->sp) HIPCHK(hipMemsetAsync(A.xflag, 0, (size_t)d->nchains * 2 * sizeof(int), d->stream));   /* exchange sequence restarts */
   if (d->have_events) HIPCHK(hipEventRecord(d->ev0, d->stream));
   if (d->jit) {   /* the run-time specialised kernel (same arguments; LDS columns: one workgroup per chain) */
@@ -4045,7 +3667,7 @@ extern "C" double srk_last_ms(srk_dev *d)
 }
 
 extern "C" int srk_block_threads(const srk_dev *d) { return d->TB; }
-extern "C" int srk_variant(const srk_dev *d) { return d->gm ? (d->sp ? 3 : 1) : (d->pr ? 2 : 0); }
+extern "C" int srk_variant(const srk_dev *d) { return d->gm ? (d->sp ? 3 : 1) : 0; }   /* (2: the retired pair kernel) */
 extern "C" int srk_specialized(const srk_dev *d) { return d->jit ? (d->jemb ? 2 : 1) : 0; }   /* 2: embedded */
 
 extern "C" int srk_fetch_dbg(srk_dev *d, unsigned long long *out)
@@ -4444,7 +4066,7 @@ __global__ void __launch_bounds__(64) sr_decide_selftest_kernel(const int *sums,
   const double aC = __builtin_fabs(K.cc) + __builtin_fabs(K.d), aD = __builtin_fabs(K.dd) + __builtin_fabs(K.c);
   double Sp, Ebp;
   int Knz;
-  const int cls = pc_classify(sums[4 * m], sums[4 * m + 1], sums[4 * m + 2], sums[4 * m + 3], K, aC, aD, false, uw[m], Sp,
+  const int cls = pc_classify(sums[4 * m], sums[4 * m + 1], sums[4 * m + 2], sums[4 * m + 3], K, aC, aD, uw[m], Sp,
                               Ebp, Knz);
   int res = 0;
   if (cls != 0) {

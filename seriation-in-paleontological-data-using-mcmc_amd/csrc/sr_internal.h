@@ -79,8 +79,8 @@ int srk_device_count(void);
 int srk_create(const sr_state_host *st, int device, int block_threads, int rec_cap_calls, int gm_force,
                const uint32_t *pkey, int spec, srk_dev **out);
 /* the kernel a session of this shape would run, without a GPU: *lds_cols 1 for LDS columns, *shape the
- * specialised kernel's shape (valid when the function returns 1); 0 no specialised kernel (HBM columns,
- * pair kernel), negative: unsupported */
+ * specialised kernel's shape (valid when the function returns 1); 0 no specialised kernel (HBM columns),
+ * negative: unsupported */
 int srk_plan(int N, int M, int nh, int block_threads, int gm_force, int manycd, sr_spec_shape *shape);
 int srk_set_stream(srk_dev *d, void *stream);
 /* calls*spc sweeps for all chains; save -> records appended at slot rec_base.. */
@@ -88,7 +88,7 @@ int srk_run(srk_dev *d, int calls, int spc, int save, int rec_base);
 int srk_sync(srk_dev *d);
 double srk_last_ms(srk_dev *d);
 int srk_block_threads(const srk_dev *d);
-int srk_variant(const srk_dev *d);   /* 0 LDS columns, 1 HBM columns */
+int srk_variant(const srk_dev *d);   /* 0 LDS columns, 1 HBM columns, 3 HBM columns and split chains (2: retired) */
 int srk_specialized(const srk_dev *d);   /* 1: the run-time specialised kernel */
 int srk_fetch_dbg(srk_dev *d, unsigned long long *out);
 int srk_fetch_records(srk_dev *d, int first, int count, int16_t *ab_pi, double *cdl);

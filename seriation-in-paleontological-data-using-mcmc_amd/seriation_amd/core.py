@@ -177,9 +177,9 @@ class Session:
 
     @property
     def kernel(self):
-        """"pair" (two lanes per taxon), "split" (HBM columns, two workgroups per chain) or "single"
-        (one workgroup per chain, one thread per taxon or several)."""
-        return {2: "pair", 3: "split"}.get(L.lib().sr_session_variant(self.h), "single")
+        """"split" (HBM columns, two workgroups per chain) or "single" (one workgroup per chain, one
+        thread per taxon or several)."""
+        return "split" if L.lib().sr_session_variant(self.h) == 3 else "single"
 
     @property
     def specialized(self):

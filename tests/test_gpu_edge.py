@@ -328,19 +328,19 @@ def test_johnk_beta_branch(columns):
         assert summ[k]["consistent"] == 0
 
 
-PAIR_CASES = [("synth-like", 256, 512, 12), ("m300", 200, 300, 5), ("n287", 287, 400, 9), ("nh0", 128, 260, 0)]
+WALK9_CASES = [("synth-like", 256, 512, 12), ("m300", 200, 300, 5), ("n287", 287, 400, 9), ("nh0", 128, 260, 0)]
 
 
-@pytest.mark.parametrize("name,N,M,nh", PAIR_CASES, ids=[c[0] for c in PAIR_CASES])
-def test_pair_kernel_parity(monkeypatch, name, N, M, nh):
-    """The opt-in pair kernel (SR_KERNEL=pair: two lanes per taxon, each walking half of a Gibbs
-    column; proposal terms in slot pairs) is bit-exact too (it is slower: DESIGN.md section 4)."""
-    monkeypatch.setenv("SR_KERNEL", "pair")
+@pytest.mark.parametrize("name,N,M,nh", WALK9_CASES, ids=[c[0] for c in WALK9_CASES])
+def test_walk9_shapes_at_the_287_site_boundary_parity(name, N, M, nh):
+    """Walks of at most 9 words (N <= 287, the last such N among them) over 257..512 taxa, with and
+    without hard sites: the default kernel -- one thread per taxon, 512 threads, the column's walk
+    words in registers -- is bit-exact.  (The shapes the retired pair kernel was tested on.)"""
     text = make_text(N, M, nh, seed=N * 1000 + M + 7)
     ds = sa.Dataset.parse(text, maxs=0)
     seeds = [4, 19]
     with sa.Session(ds, seeds) as s:
-        assert s.kernel == "pair" and s.block_threads == 1024
+        assert s.kernel == "single" and s.variant == "lds" and s.block_threads == 512
     summ, (ri, rd) = sa.run_chains(ds, seeds, burnin_calls=3, sample_calls=4, keep_records=True)
     for k, s in enumerate(seeds):
         o = oracle_ref.run_chain(text, s, 3, 4, maxs=0)

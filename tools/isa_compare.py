@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of two device assemblies of csrc/sr_device.hip (hipcc -S --cuda-device-only):
-   tools/isa_compare.py OLD.s NEW.s
+   tools/isa_compare.py [--rename-old REGEX REPL] OLD.s NEW.s
 For every function: sha256 of its instructions (label to .Lfunc_end; the __hip_cuid_<hash> word, which follows the
 source text, replaced by a fixed one) and the .amdhsa_ / resource figures of its kernel descriptor that matter here
-(VGPRs, SGPRs, spills, scratch, LDS, code bytes).  Prints one row per function: equal or the figures side by side."""
+(VGPRs, SGPRs, spills, scratch, LDS, code bytes).  Prints one row per function: equal or the figures side by side.
+Before hashing, a line loses its `;` comment and trailing blanks, runs of blanks become one, and the function's index
+within the unit goes from the local labels (.LBB<k>_, BB<k>_, .Ltmp<k>, .Lfunc_begin<k>, .Lfunc_end<k>): a function
+added or removed earlier in the unit shifts that index in every function after it.
+--rename-old applies re.sub(REGEX, REPL) to OLD's text (write REGEX to match symbol names only), for a kernel whose
+template parameters changed: its label, and its name in the kernel descriptor and section lines of its body."""
+import argparse
 import hashlib
 import re
 import subprocess
-import sys
 
 KEYS = ("NumVgprs", "NumAgprs", "NumSgprs", "ScratchSize", "Occupancy", "codeLenInByte", "LDSByteSize")
+LOCAL = re.compile(r"(\.LBB|\bBB|\.Ltmp|\.Lfunc_begin|\.Lfunc_end)\d+")
 
 
 def demangle(names):
@@ -20,9 +26,17 @@ def demangle(names):
         return {n: n for n in names}
 
 
-def functions(path):
+def normalise(ln):
+    """One instruction line as it is hashed, or None for a line that was only a comment or blank."""
+    ln = re.sub(r"\s+", " ", ln.split(";", 1)[0]).strip()
+    return LOCAL.sub(r"\1#", ln) or None
+
+
+def functions(path, rename=None):
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_X", open(path).read())
-    out, name, body = {}, None, []
+    if rename:   # everywhere the symbol stands: its label, and its kernel descriptor and section lines inside the body
+        text = re.sub(rename[0], rename[1], text)
+    out, name, body, last = {}, None, [], None
     for ln in text.splitlines():
         m = re.match(r"^(_Z\w+|sr_\w+):\s*(;.*)?$", ln)
         if name is None and m:
@@ -31,23 +45,26 @@ def functions(path):
         if name is not None:
             if ln.startswith(".Lfunc_end"):
                 out[name] = {"sha": hashlib.sha256("\n".join(body).encode()).hexdigest()[:16]}
-                cur, name = name, None
-                out[cur]["_open"] = True
+                last, name = name, None
             else:
-                body.append(ln)
+                ln = normalise(ln)
+                if ln:
+                    body.append(ln)
+            continue
         for k in KEYS:   # the "; NumVgprs: 256" comment block after each function
             m2 = re.match(r"^;\s*%s\s*[:=]\s*(\d+)" % k, ln)
-            if m2:
-                last = [n for n, v in out.items() if v.get("_open")]
-                if last:
-                    out[last[-1]][k] = int(m2.group(1))
-    for v in out.values():
-        v.pop("_open", None)
+            if m2 and last:
+                out[last][k] = int(m2.group(1))
     return out
 
 
 def main():
-    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--rename-old", nargs=2, metavar=("REGEX", "REPL"))
+    ap.add_argument("old")
+    ap.add_argument("new")
+    args = ap.parse_args()
+    a, b = functions(args.old, args.rename_old), functions(args.new)
     names = sorted(set(a) | set(b))
     dm = demangle(names)
     differ = 0
@@ -59,7 +76,7 @@ def main():
                                                                     fa.get("ScratchSize"), fa.get("codeLenInByte")))
         else:
             differ += 1
-            print("%-72s DIFFERS" % short)
+            print("%-72s %s" % (short, "DIFFERS" if fa and fb else "only in old" if fa else "only in new"))
             for tag, f in (("old", fa), ("new", fb)):
                 print("    %s %s" % (tag, f and " ".join("%s=%s" % kv for kv in sorted(f.items()))))
     print("%d functions, %d differ" % (len(names), differ))
