@@ -280,6 +280,48 @@ int sr_session_diagnostics(sr_session *s, const int32_t *chains, int32_t n_sel, 
 int sr_diag_reduce(int32_t W, int32_t n_sel, int32_t count, int32_t max_lag, const int64_t *P, const int64_t *F,
                    const int64_t *B, const int64_t *S1, const double *cdl, double *rhat, double *ess, int32_t *cut_lag);
 
+/* ---- posterior marginals over saved samples: exact histograms, quantiles, modes, means ----
+ * (an extension: the reference has none).  Records are rows [a (M) | b (M) | pi (N)] int16, W = 2M + N, with
+ * pi[site] = position; chains in selection order, as for sr_posterior.  Every column has N + 1 bins for the values
+ * 0..N (limits lie in [0, N]; positions in [0, N-1], so a pi column's bin N stays 0 for a sampler's records).
+ * flip [n_sel] (NULL = none) reflects a flagged chain's rows before counting -- the likelihood is unchanged when the
+ * order is reflected (position p -> N-1-p, alive interval [a, b) -> [N-b, N-a)), so chains of a dataset without hard
+ * sites may settle in mirrored orders and must be oriented before they are pooled: the a column of taxon m takes
+ * N - b_m, its b column N - a_m, a pi column N - 1 - pi.
+ *   hist [W][N+1]     the number of the n_sel * count samples whose (possibly reflected) value is v
+ *   outside [W]       values outside [0, N] after reflection (host records may hold any int16): counted here only
+ *   pi_sum [n_sel][N] per-chain sum of the raw, unreflected pi column (the input of an orientation decision)
+ * and per column j, with T_j the sum of hist[j] and C_j(v) its cumulative count, for each of n_probs <= 16
+ * probabilities p in [0, 1]:
+ *   quant [n_probs][W]  min{v : C_j(v) >= k}, k = clamp(ceil(p * (double)T_j), 1, T_j) (one f64 multiply, one ceil):
+ *                       the k-th smallest in-range value, p = 0.5 the lower median
+ *   mode [W]            the bin with the largest count, the lowest on ties
+ *   mean [W]            (sum_v v hist[j][v]) / T_j: the numerator exact in int64, one f64 division
+ * T_j = 0: quant = mode = -1, mean = NaN.  Integers, or one correctly rounded f64 operation on exact integers:
+ * the result does not depend on the order of the sums.  Every output pointer is optional (NULL = skip).
+ * SR_EINVAL: n_sel <= 0, count < 1, n_sel * count >= 2^31, n_probs outside [0, 16], a p outside [0, 1] or NaN,
+ * N > 32767; the session form also for rows beyond the buffered records or a chain index out of range.  The
+ * histograms are built on the GPU in column batches of at most 256 MB, so a call without hist works for any N. */
+typedef struct {
+  const uint8_t *flip;     /* in: [n_sel] or NULL */
+  const double *probs;     /* in: [n_probs] */
+  int32_t n_probs;
+  uint32_t *hist;          /* out: [W][N+1], NULL = skip */
+  uint32_t *outside;       /* out: [W] */
+  int64_t *pi_sum;         /* out: [n_sel][N] */
+  int32_t *quant, *mode;   /* out: [n_probs][W], [W] */
+  double *mean;            /* out: [W] */
+  double kernel_ms;        /* out */
+} sr_marg_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M */
+int sr_marginals(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                 sr_marg_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order); the session's state
+   and records are left untouched */
+int sr_session_marginals(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                         sr_marg_out *out);
+
 const char *sr_strerror(int code);
 int sr_device_count(void);
 const char *sr_version(void);

@@ -1338,6 +1338,61 @@ SR_API int sr_session_diagnostics(sr_session *s, const int32_t *chains, int32_t 
   return rc;
 }
 
+/* ---- posterior marginals: histograms, quantiles, modes, means (definitions: include/seriation.h) ---- */
+/* sr_marg.hip's entry points, weak for the same reason as the moment kernels' */
+extern __typeof__(srm_marginals_dev) srm_marginals_dev __attribute__((weak));
+extern __typeof__(srm_marginals_host) srm_marginals_host __attribute__((weak));
+
+/* the argument checks both forms share, made before any device call */
+static int marg_check(const sr_marg_out *out, int32_t n_sel, int32_t count)
+{
+  if (!out || n_sel <= 0 || count < 1 || (int64_t)n_sel * count >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (out->n_probs < 0 || out->n_probs > 16 || (out->n_probs > 0 && !out->probs)) return SR_EINVAL;
+  for (int q = 0; q < out->n_probs; q++)
+    if (!(out->probs[q] >= 0.0 && out->probs[q] <= 1.0)) return SR_EINVAL;   /* NaN included */
+  return SR_OK;
+}
+
+SR_API int sr_marginals(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                        sr_marg_out *out)
+{
+  if (!ds || !ab_pi || ds->N < 1 || ds->N > 32767 || ds->M < 1) return SR_EINVAL;
+  int rc = marg_check(out, n_sel, count);
+  if (rc) return rc;
+  if (!srm_marginals_host) return SR_EUNSUPPORTED;
+  float ms = 0.0f;
+  rc = srm_marginals_host(device, ab_pi, n_sel, count, ds->N, ds->M, out->flip, out->probs, out->n_probs, out->hist,
+                          out->outside, (long long *)out->pi_sum, out->quant, out->mode, out->mean, &ms);
+  out->kernel_ms = ms;
+  return post_rc(rc);
+}
+
+SR_API int sr_session_marginals(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                sr_marg_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = marg_check(out, n_sel, count);
+  if (rc) return rc;
+  if (first < 0 || first > s->nrec || count > s->nrec - first || s->ds.N > 32767) return SR_EINVAL;
+  for (int k = 0; k < n_sel; k++)
+    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  if (!srm_marginals_dev) return SR_EUNSUPPORTED;
+  const int16_t *rec;
+  int cap, dev;
+  void *stream;
+  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
+  const long long W = 2LL * s->ds.M + s->ds.N;
+  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
+  if (!off) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
+  float ms = 0.0f;
+  rc = srm_marginals_dev(dev, stream, rec, off, n_sel, count, W, s->ds.N, s->ds.M, out->flip, out->probs, out->n_probs,
+                         out->hist, out->outside, (long long *)out->pi_sum, out->quant, out->mode, out->mean, &ms);
+  out->kernel_ms = ms;
+  free(off);
+  return post_rc(rc);
+}
+
 SR_API void sr_session_destroy(sr_session *s)
 {
   if (!s) return;

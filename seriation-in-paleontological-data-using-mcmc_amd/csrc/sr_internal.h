@@ -129,6 +129,18 @@ int srd_moments_dev(int device, void *stream, const int16_t *d_rec, const long l
                     float *ms);
 int srd_moments_host(int device, const int16_t *ab_pi, int n_sel, int count, int W, int L, long long *P, long long *F,
                      long long *B, long long *S1, float *ms);
+/* posterior marginals (sr_marg.hip): the exact histograms of every record column over n_sel chains' `count` rows
+   (bins 0..N, a flagged chain's rows reflected) and what is read off them; flip [n_sel] (or NULL) and probs [Q]
+   (Q <= 16) are host inputs, hist [W][N+1], outside [W], pi_sum [n_sel][N], quant [Q][W], mode [W], mean [W] host
+   buffers, each optional.  Weak in sr_host.c like the moment kernels: sr_marginals returns SR_EUNSUPPORTED in
+   the host-only builds. */
+int srm_marginals_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
+                      long long row_stride, int N, int M, const uint8_t *flip, const double *probs, int Q,
+                      uint32_t *hist, uint32_t *outside, long long *pi_sum, int32_t *quant, int32_t *mode, double *mean,
+                      float *ms);
+int srm_marginals_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *flip,
+                       const double *probs, int Q, uint32_t *hist, uint32_t *outside, long long *pi_sum,
+                       int32_t *quant, int32_t *mode, double *mean, float *ms);
 void srk_destroy(srk_dev *d);
 
 #ifdef __cplusplus

@@ -7,6 +7,7 @@ Layers (reference file in parentheses):
   dist      chain sharding + the one all-gather (RCCL)     (replaces script.py's Pool(8))
   analysis  E[c], E[d], CORRMN, pair-order matrix          (script.py:102-189)
             split-R-hat / ESS convergence diagnostics      (an extension: no counterpart)
+            posterior marginals: quantiles, modes, means   (an extension: no counterpart)
 """
 from ._lib import SrError, LIB_PATH, lib  # noqa: F401
 from .core import Dataset, Session, run_chains, run_to_dirs, specialize  # noqa: F401

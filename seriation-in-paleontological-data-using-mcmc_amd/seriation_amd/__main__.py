@@ -7,12 +7,17 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
     python -m seriation_amd DATASET [--chains 100] [--burnin 1000] [--samples 1000] [--thin 10]
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
+                                    [--marginals]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
                 script.py:25-38 (at most 256 chains)
   --select K    after the run, the one-sigma selection of choose_chains (script.py:70-98) over
                 the written exp_data.csv files; prints the chosen chain indices
+  --marginals   with --select: the posterior marginals of the chosen chains (analysis.marginals_from_records
+                over their chain_data.csv, mirrored chains oriented first) into Chains/marginals.csv, one line
+                per record column: kind (a, b, pi), index, mean, mode, the 2.5 %, 50 % and 97.5 % quantiles and
+                the count of out-of-range values
   --no-save     sample without writing files; prints one JSON summary per chain
   --rng         mt: GSL MT19937 as the reference (default); philox: the opt-in counter-based
                 Philox4x32-10 stream for sampling (statistically equivalent, not bit-equal)
@@ -25,10 +30,27 @@ fails its closing consistency check (mcmc.c:199-204).
 """
 import argparse
 import json
+import os
 import sys
 import time
 
 from . import core, launcher
+
+
+def write_marginals(ds, chains, root, device=0):
+    """Chains/marginals.csv of the chosen chains: their chain_data.csv rows, oriented against the first chain,
+    pooled into one marginal per record column."""
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    flips = analysis.chain_orientation(analysis.marginals_from_records(ds, rec, probs=(), device=device)["pi_sum"])
+    r = analysis.marginals_from_records(ds, rec, probs=analysis.PROBS, flips=flips, device=device)
+    with open(os.path.join(root, "Chains", "marginals.csv"), "w") as fh:
+        fh.write("kind,index,mean,mode,%s,outside\n" % ",".join("q%s" % p for p in analysis.PROBS))
+        for kind in ("a", "b", "pi"):
+            for j in range(len(r["mode"][kind])):
+                fh.write("%s,%d,%r,%d,%s,%d\n" % (kind, j, float(r["mean"][kind][j]), r["mode"][kind][j],
+                                                  ",".join(str(q) for q in r["quant"][kind][:, j]),
+                                                  r["outside"][kind][j]))
 
 
 def main(argv=None):
@@ -46,7 +68,10 @@ def main(argv=None):
     ap.add_argument("--debug-check", action="store_true")
     ap.add_argument("--rng", default="mt", choices=("mt", "philox"))
     ap.add_argument("--manycd", action="store_true")
+    ap.add_argument("--marginals", action="store_true")
     a = ap.parse_args(argv)
+    if a.marginals and (a.select < 1 or a.no_save):
+        ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
     if a.chains < 1 or a.burnin < 0 or a.samples < 0 or a.thin < 1:
         ap.error("--chains and --thin must be >= 1, --burnin and --samples >= 0")
     devices = [int(d) for d in a.devices.split(",") if d.strip()]
@@ -74,7 +99,10 @@ def main(argv=None):
                                        burnin_calls=a.burnin, sample_calls=a.samples, root=a.root,
                                        sweeps_per_call=a.thin, rng=a.rng, manycd=int(a.manycd))
         if a.select:
-            print("selected:", " ".join(str(k) for k in launcher.choose_chains(a.select, a.root)))
+            chosen = launcher.choose_chains(a.select, a.root)
+            print("selected:", " ".join(str(k) for k in chosen))
+            if a.marginals:
+                write_marginals(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
     return 1 if any(s.get("consistent", 0) for s in summ) else 0
 
 

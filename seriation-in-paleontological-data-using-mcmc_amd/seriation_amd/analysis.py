@@ -244,6 +244,98 @@ def diag_reduce(P, F, B, S1, count, max_lag=0, cdl=None):
     return rhat, ess, cut
 
 
+# ---------------------------------------------------------------- posterior marginals
+# Where each site and each taxon limit lies, and how sure: the exact histogram of every record column over the
+# selected chains, and the quantiles, mode and mean read off it (definitions: include/seriation.h).  Histograms and
+# summaries come from the GPU (csrc/sr_marg.hip); there is no CPU fallback.  Chains of a dataset without hard sites
+# may settle in mirrored orders: orient them first (chain_orientation) or the pooled numbers mean nothing.
+PROBS = (0.025, 0.5, 0.975)
+
+
+def _marg_views(flat, N, M):
+    """[..., 2M+N] -> views of the a, b and pi columns."""
+    return {"a": flat[..., :M], "b": flat[..., M:2 * M], "pi": flat[..., 2 * M:2 * M + N]}
+
+
+def _marg_outs(N, M, n_sel, probs, flips, hist):
+    W = 2 * M + N
+    p = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    n_sel = max(int(n_sel), 0)
+    flat = {"quant": np.zeros((len(p), W), np.int32), "mode": np.zeros(W, np.int32), "mean": np.zeros(W),
+            "outside": np.zeros(W, np.uint32)}
+    pi_sum = np.zeros((n_sel, N), np.int64)
+    out = L.sr_marg_out()
+    keep = [p, pi_sum]   # the buffers the struct points into
+    if flips is not None:
+        f = np.ascontiguousarray(np.asarray(flips) != 0, dtype=np.uint8)
+        assert f.shape == (n_sel,)
+        out.flip = f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        keep.append(f)
+    out.probs = p.ctypes.data_as(_DBLP)
+    out.n_probs = len(p)
+    out.quant = flat["quant"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    out.mode = flat["mode"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    out.mean = flat["mean"].ctypes.data_as(_DBLP)
+    out.outside = flat["outside"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    out.pi_sum = pi_sum.ctypes.data_as(_I64P)
+    h = None
+    if hist:
+        h = np.zeros((W, N + 1), np.uint32)
+        out.hist = h.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+    return out, flat, pi_sum, h, keep
+
+
+def _marg_result(out, flat, pi_sum, h, N, M):
+    res = {k: _marg_views(v, N, M) for k, v in flat.items()}
+    res["pi_sum"] = pi_sum
+    res["kernel_ms"] = out.kernel_ms
+    if h is not None:
+        res["hist"] = h
+    return res
+
+
+def marginals_from_records(dataset, ab_pi, probs=PROBS, flips=None, hist=False, device=0):
+    """sr_marginals: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order) -> {"quant": {"a":
+    [Q][M], "b": [Q][M], "pi": [Q][N]} (one row per probability), "mode", "mean", "outside": {"a": [M], "b": [M],
+    "pi": [N]}, "pi_sum": [n_sel][N] (per-chain sums of the raw pi columns), "kernel_ms"}; hist=True adds "hist"
+    [2M+N][N+1] uint32.  flips [n_sel]: chains whose rows are reflected before counting."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    out, flat, pi_sum, h, _keep = _marg_outs(dataset.N, dataset.M, n_sel, probs, flips, hist)
+    _check(L.lib().sr_marginals(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n_sel,
+                                count, device, ctypes.byref(out)), "sr_marginals")
+    return _marg_result(out, flat, pi_sum, h, dataset.N, dataset.M)
+
+
+def marginals_from_session(session, chains, first=0, count=None, probs=PROBS, flips=None, hist=False):
+    """sr_session_marginals: the same over a session's records still in HBM, rows [first, first + count) of
+    chains (session chain indices in selection order)."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, flat, pi_sum, h, _keep = _marg_outs(session.ds.N, session.ds.M, len(chains), probs, flips, hist)
+    _check(L.lib().sr_session_marginals(session.h, ch, len(chains), first, count, ctypes.byref(out)),
+           "sr_session_marginals")
+    return _marg_result(out, flat, pi_sum, h, session.ds.N, session.ds.M)
+
+
+def chain_orientation(pi_sum):
+    """pi_sum [n_sel][N] (marginals' per-chain sums of the pi columns) -> uint8 [n_sel]: 1 for a chain whose order
+    runs against chain 0's, i.e. whose Pearson correlation with pi_sum[0] is negative (zero or undefined: 0).  The
+    sign is that of n sum(xy) - sum(x) sum(y), taken in exact integers.  Intended use: one marginals call for
+    pi_sum, then one with flips=chain_orientation(pi_sum)."""
+    rows = [[int(v) for v in r] for r in np.asarray(pi_sum).tolist()]
+    out = np.zeros(len(rows), np.uint8)
+    if not rows:
+        return out
+    x, n = rows[0], len(rows[0])
+    sx = sum(x)
+    for k, y in enumerate(rows):
+        cov = n * sum(a * b for a, b in zip(x, y)) - sx * sum(y)
+        out[k] = 1 if cov < 0 else 0
+    return out
+
+
 def read_chain_rows(root, chains, sites, taxa):
     """chain_data.csv of each chain -> int16 [n][lines][2M+N] (fields 0, 1, 2 tokens as the script
     slices them).  All chains must hold the same number of lines."""

@@ -80,7 +80,7 @@ def choose_chains(chains_selected, root="."):
     in ascending value, returned as sorted chain indices.  Quirks kept: strict window,
     ddof=0, mapping back by float equality over the directory listing."""
     chains_dir = os.path.join(root, "Chains")
-    dirs = os.listdir(chains_dir)
+    dirs = [d for d in os.listdir(chains_dir) if d.startswith("chain_")]   # (not the CLI's marginals.csv)
     vals = [_read_exp_loglik(os.path.join(chains_dir, d, "exp_data.csv")) for d in dirs]
     return choose_from_values(dict(zip(dirs, vals)), chains_selected)
 
