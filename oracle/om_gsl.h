@@ -24,6 +24,16 @@
  * ziggurat stream is pinned only through the regenerated tables (tools/gen_tables.py
  * reproduces the published ytab/ktab/wtab head values); GSL itself is absent here.
  * libm exp/log are replaced by om_exp/om_log (om_libm.h).
+ *
+ * Checked by the reference executing (tests/test_reference_exec.py; oracle/Makefile builds the
+ * reference's unmodified mcmc.c over the stand-in ref/gsl/, whose generator and distributions
+ * forward to this file): the transcription om_mcmc.c, call by call and byte by byte, on the main
+ * path, manycd = 1, hard sites, zero columns, the Johnk branch and seed 0; and om_exp / om_log
+ * against the machine's real exp / log, which the reference calls there, on every value those
+ * chains pass through.  NOT checked by it: anything in this file against real GSL -- the
+ * stand-in is this file, so the gamma / ziggurat stream stays unpinned.  One known difference
+ * it cannot see: om_gamma's a < 1 branch below writes exp(log(u) / a) where GSL calls
+ * pow(u, 1 / a); the sampler passes a = 1 + count >= 1 and never takes that branch.
  */
 #ifndef OM_GSL_H
 #define OM_GSL_H
@@ -240,7 +250,9 @@ static inline double om_gaussian_ziggurat(om_rng *r, double sigma)
 static inline double om_gamma(om_rng *r, double a, double b)
 {
   if (a < 1) {
-    /* GSL boost: gamma(1+a) * pow(u, 1/a).  Unreachable from the sampler (a = 1 + count). */
+    /* GSL boost: gamma(1+a) * pow(u, 1/a), written here as exp(log(u) / a): not the same bits as
+       GSL's pow in general.  Unreachable from the sampler (mcmc.c:757 passes a = 1 + count >= 1), so
+       neither the chains nor the reference run over the stand-in (which forwards here) can see it. */
     double u = om_uniform_pos(r);
     return om_gamma(r, 1.0 + a, b) * om_exp(om_log(u) * (1.0 / a));
   }

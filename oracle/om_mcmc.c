@@ -14,8 +14,10 @@
  *   - plain int arrays instead of gsl_vector/gsl_permutation (same values);
  *   - mcmc_randomize's read of q[nh] past the end (mcmc.c:530, UB) is guarded;
  *   - the library entry points return error codes instead of exit(1).
- * Parity with the reference binary itself is UNPINNED for the gamma/ziggurat stream
- * (GSL is not available in this container); see DESIGN.md "Oracle".
+ * This file is checked against the reference's own source executing over a GSL stand-in
+ * (oracle/ref/, tests/test_reference_exec.py).  Parity with the reference binary itself stays
+ * UNPINNED for the gamma/ziggurat stream (GSL is not available; the stand-in forwards to
+ * om_gsl.h); see DESIGN.md "Oracle and parity".
  */
 #include <stdio.h>
 #include <stdlib.h>

@@ -21,4 +21,7 @@ def shapes():
     out |= {(256, 300, 5, 0), (400, 150, 5, 0),   # test_gpu_edge.test_steep_walks
             (70, 90, 3, 0), (70, 90, 9, 0),      # test_gpu_jit shards, test_gpu_multi
             (40, 24, 3, 0)}                      # test_gpu_edge.test_johnk_beta_branch
+    import ref_exec
+    out |= {(src["N"], src["M"], src["nh"], 0) for _, src, _, _, _ in ref_exec.FIXTURE_CASES   # test_gpu_reference_exec
+            if not isinstance(src, str)}
     return sorted(out)
