@@ -322,6 +322,46 @@ int sr_marginals(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int3
 int sr_session_marginals(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
                          sr_marg_out *out);
 
+/* ---- taxon-pair relations, durations and the diversity curve over saved samples: exact counts ----
+ * (an extension: the reference has none).  Joint functions of the limits, which no per-column output can give.
+ * Records are rows [a (M) | b (M) | pi (N)] int16 as above; only the first 2M entries of a row are read; chains in
+ * selection order.  flip [n_sel] (NULL = none) reflects a flagged chain's rows first, as in sr_marginals:
+ * a'_m = N - b_m, b'_m = N - a_m.  All arithmetic is int32: any int16 input is legal and nothing wraps
+ * (N - (-32768) is simply a large value).  T = n_sel * count samples; taxon m is alive at position p when
+ * a_m <= p < b_m.
+ * Pair matrices, each [M][M] uint32, entry [i][j] the number of the T samples with
+ *   orig_before   a_i < a_j                          i originates strictly earlier
+ *   ext_before    b_i < b_j                          i ends strictly earlier
+ *   precedes      b_i <= a_j                         i is over before j begins; the diagonal counts empty intervals
+ *   overlap       max(a_i, a_j) < min(b_i, b_j)      i and j share a position; symmetric; the diagonal counts
+ *                                                    non-empty intervals
+ * (pure comparisons: no value is "outside" for them).  Per taxon:
+ *   dur_hist [M][N+1]   the samples with b_m - a_m = v, v in 0..N (unchanged by a reflection)
+ *   dur_outside [M]     the samples whose difference lies outside [0, N]
+ * Per position:
+ *   rich_hist [N][M+1]  entry [p][r]: the samples in which exactly r taxa are alive at position p, p in 0..N-1;
+ *                       defined for any input (limits beyond [0, N] simply clamp); every row sums to T
+ * Every output pointer is optional (NULL = skip); a call only pays for what it asks.
+ * SR_EINVAL: NULL ds, ab_pi or out, n_sel <= 0, count < 1, n_sel * count >= 2^31, N outside 1..32767, M < 1; the
+ * session form also for rows beyond the buffered records or a chain index out of range.  SR_EUNSUPPORTED: a single
+ * requested output larger than 1 GiB (a pair matrix with M > 16384, dur_hist with M (N+1) > 2^28, rich_hist with
+ * N (M+1) > 2^28), or a library built without the device layer.  All reported before any device call. */
+typedef struct {
+  const uint8_t *flip;                                       /* in: [n_sel] or NULL */
+  uint32_t *orig_before, *ext_before, *precedes, *overlap;   /* out: [M][M] each */
+  uint32_t *dur_hist, *dur_outside;                          /* out: [M][N+1], [M] */
+  uint32_t *rich_hist;                                       /* out: [N][M+1] */
+  double kernel_ms;                                          /* out */
+} sr_rel_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M */
+int sr_relations(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                 sr_rel_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order), on the session's
+   stream; the session's state and records are left untouched */
+int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                         sr_rel_out *out);
+
 const char *sr_strerror(int code);
 int sr_device_count(void);
 const char *sr_version(void);

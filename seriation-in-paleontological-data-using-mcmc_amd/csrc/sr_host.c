@@ -1393,6 +1393,68 @@ SR_API int sr_session_marginals(sr_session *s, const int32_t *chains, int32_t n_
   return post_rc(rc);
 }
 
+/* ---- taxon-pair relations, durations, richness: exact counts (definitions: include/seriation.h) ---- */
+/* sr_rel.hip's entry points, weak for the same reason as the moment kernels' */
+extern __typeof__(srr_relations_dev) srr_relations_dev __attribute__((weak));
+extern __typeof__(srr_relations_host) srr_relations_host __attribute__((weak));
+
+#define REL_OUT_MAX ((int64_t)1 << 28)   /* uint32 entries of one output: 1 GiB */
+
+/* the argument checks both forms share, made before any device call */
+static int rel_check(const sr_rel_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (!out || n_sel <= 0 || count < 1 || (int64_t)n_sel * count >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  if ((out->orig_before || out->ext_before || out->precedes || out->overlap) && (int64_t)M * M > REL_OUT_MAX)
+    return SR_EUNSUPPORTED;
+  if (out->dur_hist && (int64_t)M * (N + 1) > REL_OUT_MAX) return SR_EUNSUPPORTED;
+  if (out->rich_hist && (int64_t)N * ((int64_t)M + 1) > REL_OUT_MAX) return SR_EUNSUPPORTED;
+  return SR_OK;
+}
+
+SR_API int sr_relations(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                        sr_rel_out *out)
+{
+  if (!ds || !ab_pi) return SR_EINVAL;
+  int rc = rel_check(out, n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!srr_relations_host) return SR_EUNSUPPORTED;
+  uint32_t *const pair[4] = {out->orig_before, out->ext_before, out->precedes, out->overlap};
+  float ms = 0.0f;
+  rc = srr_relations_host(device, ab_pi, n_sel, count, ds->N, ds->M, out->flip, pair, out->dur_hist, out->dur_outside,
+                          out->rich_hist, &ms);
+  out->kernel_ms = ms;
+  return post_rc(rc);
+}
+
+SR_API int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                sr_rel_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = rel_check(out, n_sel, count, s->ds.N, s->ds.M);
+  if (rc == SR_EINVAL) return rc;
+  if (first < 0 || first > s->nrec || count > s->nrec - first) return SR_EINVAL;
+  for (int k = 0; k < n_sel; k++)
+    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  if (rc) return rc;
+  if (!srr_relations_dev) return SR_EUNSUPPORTED;
+  const int16_t *rec;
+  int cap, dev;
+  void *stream;
+  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
+  const long long W = 2LL * s->ds.M + s->ds.N;
+  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
+  if (!off) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
+  uint32_t *const pair[4] = {out->orig_before, out->ext_before, out->precedes, out->overlap};
+  float ms = 0.0f;
+  rc = srr_relations_dev(dev, stream, rec, off, n_sel, count, W, s->ds.N, s->ds.M, out->flip, pair, out->dur_hist,
+                         out->dur_outside, out->rich_hist, &ms);
+  out->kernel_ms = ms;
+  free(off);
+  return post_rc(rc);
+}
+
 SR_API void sr_session_destroy(sr_session *s)
 {
   if (!s) return;

@@ -141,6 +141,16 @@ int srm_marginals_dev(int device, void *stream, const int16_t *d_rec, const long
 int srm_marginals_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *flip,
                        const double *probs, int Q, uint32_t *hist, uint32_t *outside, long long *pi_sum,
                        int32_t *quant, int32_t *mode, double *mean, float *ms);
+/* taxon-pair relations, durations, richness (sr_rel.hip): exact counts over n_sel chains' `count` rows, a flagged
+   chain's limits reflected; flip [n_sel] (or NULL) is a host input, pair[4] (orig_before, ext_before, precedes,
+   overlap: [M][M] each), dur_hist [M][N+1], dur_outside [M], rich_hist [N][M+1] host buffers, each optional.  Weak
+   in sr_host.c like the marginals' entry points: sr_relations returns SR_EUNSUPPORTED in the host-only builds. */
+int srr_relations_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
+                      long long row_stride, int N, int M, const uint8_t *flip, uint32_t *const pair[4],
+                      uint32_t *dur_hist, uint32_t *dur_outside, uint32_t *rich_hist, float *ms);
+int srr_relations_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *flip,
+                       uint32_t *const pair[4], uint32_t *dur_hist, uint32_t *dur_outside, uint32_t *rich_hist,
+                       float *ms);
 void srk_destroy(srk_dev *d);
 
 #ifdef __cplusplus

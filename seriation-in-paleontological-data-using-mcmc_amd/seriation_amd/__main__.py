@@ -7,7 +7,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
     python -m seriation_amd DATASET [--chains 100] [--burnin 1000] [--samples 1000] [--thin 10]
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
-                                    [--marginals]
+                                    [--marginals] [--relations]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -18,6 +18,11 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 over their chain_data.csv, mirrored chains oriented first) into Chains/marginals.csv, one line
                 per record column: kind (a, b, pi), index, mean, mode, the 2.5 %, 50 % and 97.5 % quantiles and
                 the count of out-of-range values
+  --relations   with --select: the relations between the chosen chains' taxa (analysis.relations_from_records over
+                their chain_data.csv, mirrored chains oriented first).  Chains/diversity.csv: per position the
+                mean and the 2.5 %, 50 % and 97.5 % quantiles of the number of taxa alive; Chains/taxon_pairs.csv:
+                per pair i < j the counts of samples in which i originates before j and j before i, i ends before
+                j and j before i, i is over before j begins and j before i begins, and the two coexist
   --no-save     sample without writing files; prints one JSON summary per chain
   --rng         mt: GSL MT19937 as the reference (default); philox: the opt-in counter-based
                 Philox4x32-10 stream for sampling (statistically equivalent, not bit-equal)
@@ -42,8 +47,7 @@ def write_marginals(ds, chains, root, device=0):
     pooled into one marginal per record column."""
     from . import analysis
     rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
-    flips = analysis.chain_orientation(analysis.marginals_from_records(ds, rec, probs=(), device=device)["pi_sum"])
-    r = analysis.marginals_from_records(ds, rec, probs=analysis.PROBS, flips=flips, device=device)
+    r = analysis.marginals_from_records(ds, rec, probs=analysis.PROBS, flips=_oriented(ds, rec, device), device=device)
     with open(os.path.join(root, "Chains", "marginals.csv"), "w") as fh:
         fh.write("kind,index,mean,mode,%s,outside\n" % ",".join("q%s" % p for p in analysis.PROBS))
         for kind in ("a", "b", "pi"):
@@ -51,6 +55,32 @@ def write_marginals(ds, chains, root, device=0):
                 fh.write("%s,%d,%r,%d,%s,%d\n" % (kind, j, float(r["mean"][kind][j]), r["mode"][kind][j],
                                                   ",".join(str(q) for q in r["quant"][kind][:, j]),
                                                   r["outside"][kind][j]))
+
+
+def _oriented(ds, rec, device):
+    """the chains' flips against the first chain, as write_marginals takes them"""
+    from . import analysis
+    return analysis.chain_orientation(analysis.marginals_from_records(ds, rec, probs=(), device=device)["pi_sum"])
+
+
+def write_relations(ds, chains, root, device=0):
+    """Chains/diversity.csv and Chains/taxon_pairs.csv of the chosen chains: their chain_data.csv rows, oriented
+    against the first chain, pooled into exact counts."""
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    r = analysis.relations_from_records(ds, rec, flips=_oriented(ds, rec, device), device=device)
+    dc = analysis.diversity_curve(r["rich_hist"], analysis.PROBS)
+    with open(os.path.join(root, "Chains", "diversity.csv"), "w") as fh:
+        fh.write("position,mean,%s\n" % ",".join("q%s" % p for p in analysis.PROBS))
+        for p in range(ds.N):
+            fh.write("%d,%r,%s\n" % (p, float(dc["mean"][p]), ",".join(str(q) for q in dc["quant"][:, p])))
+    ob, eb, pr, ov = (r[k].tolist() for k in ("orig_before", "ext_before", "precedes", "overlap"))
+    with open(os.path.join(root, "Chains", "taxon_pairs.csv"), "w") as fh:
+        fh.write("i,j,orig_ij,orig_ji,ext_ij,ext_ji,prec_ij,prec_ji,overlap\n")
+        for i in range(ds.M):
+            for j in range(i + 1, ds.M):
+                fh.write("%d,%d,%d,%d,%d,%d,%d,%d,%d\n" % (i, j, ob[i][j], ob[j][i], eb[i][j], eb[j][i], pr[i][j],
+                                                          pr[j][i], ov[i][j]))
 
 
 def main(argv=None):
@@ -69,9 +99,12 @@ def main(argv=None):
     ap.add_argument("--rng", default="mt", choices=("mt", "philox"))
     ap.add_argument("--manycd", action="store_true")
     ap.add_argument("--marginals", action="store_true")
+    ap.add_argument("--relations", action="store_true")
     a = ap.parse_args(argv)
     if a.marginals and (a.select < 1 or a.no_save):
         ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
+    if a.relations and (a.select < 1 or a.no_save):
+        ap.error("--relations needs --select K (and the chain files: not with --no-save)")
     if a.chains < 1 or a.burnin < 0 or a.samples < 0 or a.thin < 1:
         ap.error("--chains and --thin must be >= 1, --burnin and --samples >= 0")
     devices = [int(d) for d in a.devices.split(",") if d.strip()]
@@ -103,6 +136,8 @@ def main(argv=None):
             print("selected:", " ".join(str(k) for k in chosen))
             if a.marginals:
                 write_marginals(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
+            if a.relations:
+                write_relations(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
     return 1 if any(s.get("consistent", 0) for s in summ) else 0
 
 

@@ -92,6 +92,15 @@ class sr_marg_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_rel_out(ctypes.Structure):
+    _fields_ = [("flip", ctypes.POINTER(ctypes.c_uint8)),
+                ("orig_before", ctypes.POINTER(ctypes.c_uint32)), ("ext_before", ctypes.POINTER(ctypes.c_uint32)),
+                ("precedes", ctypes.POINTER(ctypes.c_uint32)), ("overlap", ctypes.POINTER(ctypes.c_uint32)),
+                ("dur_hist", ctypes.POINTER(ctypes.c_uint32)), ("dur_outside", ctypes.POINTER(ctypes.c_uint32)),
+                ("rich_hist", ctypes.POINTER(ctypes.c_uint32)),
+                ("kernel_ms", ctypes.c_double)]
+
+
 SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                            ctypes.POINTER(sr_record))
 
@@ -107,7 +116,8 @@ PUBLIC_SYMBOLS = [
     "sr_session_accept_counts", "sr_session_fallback_counts", "sr_session_debug_flagged", "sr_session_last_kernel_ms", "sr_session_block_threads", "sr_session_variant", "sr_session_specialized",
     "sr_session_checkpoint", "sr_session_restore",
     "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior",
-    "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals", "sr_strerror", "sr_device_count", "sr_version",
+    "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals",
+    "sr_relations", "sr_session_relations", "sr_strerror", "sr_device_count", "sr_version",
 ]
 
 _LIB = None
@@ -172,6 +182,8 @@ def _lib():
                                    P(ctypes.c_int64), P(c_double), P(c_double), P(c_double), P(c_i32)]),
         "sr_marginals": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_marg_out)]),
         "sr_session_marginals": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_marg_out)]),
+        "sr_relations": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_rel_out)]),
+        "sr_session_relations": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_rel_out)]),
         "sr_strerror": (ctypes.c_char_p, [c_int]),
         "sr_device_count": (c_int, []),
         "sr_version": (ctypes.c_char_p, []),

@@ -336,6 +336,76 @@ def chain_orientation(pi_sum):
     return out
 
 
+# ---------------------------------------------------------------- taxon-pair relations and the diversity curve
+# Which taxon came first, which pairs coexisted, how long each lasted and how many were alive at each position:
+# joint functions of the limits, counted exactly over the selected chains' samples (definitions:
+# include/seriation.h).  The counts come from the GPU (csrc/sr_rel.hip); there is no CPU fallback.  Orient mirrored
+# chains first, as for the marginals.
+REL_KINDS = ("orig_before", "ext_before", "precedes", "overlap", "dur_hist", "dur_outside", "rich_hist")
+
+
+def _rel_outs(N, M, n_sel, flips, kinds):
+    shapes = {"orig_before": (M, M), "ext_before": (M, M), "precedes": (M, M), "overlap": (M, M),
+              "dur_hist": (M, N + 1), "dur_outside": (M,), "rich_hist": (N, M + 1)}
+    arrs = {k: np.zeros(shapes[k], np.uint32) for k in kinds}
+    out = L.sr_rel_out()
+    keep = []   # the buffers the struct points into
+    if flips is not None:
+        f = np.ascontiguousarray(np.asarray(flips) != 0, dtype=np.uint8)
+        assert f.shape == (max(int(n_sel), 0),)
+        out.flip = f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        keep.append(f)
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    return out, arrs, keep
+
+
+def relations_from_records(dataset, ab_pi, flips=None, kinds=REL_KINDS, device=0):
+    """sr_relations: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order) -> {kind: uint32 array}
+    for the requested kinds ("orig_before", "ext_before", "precedes", "overlap": [M][M]; "dur_hist": [M][N+1];
+    "dur_outside": [M]; "rich_hist": [N][M+1]) plus "total" (the number of samples) and "kernel_ms".  flips [n_sel]:
+    chains whose limits are reflected before counting."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    out, arrs, _keep = _rel_outs(dataset.N, dataset.M, n_sel, flips, kinds)
+    _check(L.lib().sr_relations(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n_sel,
+                                count, device, ctypes.byref(out)), "sr_relations")
+    arrs["total"] = n_sel * count
+    arrs["kernel_ms"] = out.kernel_ms
+    return arrs
+
+
+def relations_from_session(session, chains, first=0, count=None, flips=None, kinds=REL_KINDS):
+    """sr_session_relations: the same over a session's records still in HBM, rows [first, first + count) of
+    chains (session chain indices in selection order)."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs, _keep = _rel_outs(session.ds.N, session.ds.M, len(chains), flips, kinds)
+    _check(L.lib().sr_session_relations(session.h, ch, len(chains), first, count, ctypes.byref(out)),
+           "sr_session_relations")
+    arrs["total"] = len(chains) * count
+    arrs["kernel_ms"] = out.kernel_ms
+    return arrs
+
+
+def diversity_curve(rich_hist, probs=PROBS):
+    """rich_hist [N][M+1] (relations' exact histogram of the number of taxa alive at each position) -> {"mean": [N]
+    f64, "quant": [len(probs)][N] int32}, on the host, by the marginals' rules: the quantile of probability p is the
+    richness at which the cumulative count first reaches the rank k = clamp(ceil(p * T), 1, T), T the position's
+    total; the mean is an exact int64 numerator divided once in f64."""
+    h = np.asarray(rich_hist).astype(np.int64)
+    assert h.ndim == 2
+    T = h.sum(axis=1)
+    cum = np.cumsum(h, axis=1)
+    quant = np.zeros((len(probs), h.shape[0]), np.int32)
+    for q, p in enumerate(probs):
+        k = np.clip(np.ceil(float(p) * T.astype(np.float64)).astype(np.int64), 1, T)
+        quant[q] = np.argmax(cum >= k[:, None], axis=1)
+    num = (h * np.arange(h.shape[1], dtype=np.int64)[None, :]).sum(axis=1)
+    return {"mean": num.astype(np.float64) / T.astype(np.float64), "quant": quant}
+
+
 def read_chain_rows(root, chains, sites, taxa):
     """chain_data.csv of each chain -> int16 [n][lines][2M+N] (fields 0, 1, 2 tokens as the script
     slices them).  All chains must hold the same number of lines."""
