@@ -362,6 +362,57 @@ int sr_relations(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int3
 int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
                          sr_rel_out *out);
 
+/* ---- WAIC and the pointwise model fit over saved samples: defined to the bit ----
+ * (an extension: the reference's choose_chains compares mean -loglik, which cannot compare the shared-rates model
+ * with the per-taxon one.)  Watanabe 2010; Vehtari, Gelman & Gabry 2017.  The likelihood factorises over the N M
+ * cells of X (mcmc_logl, mcmc.c:625-648).  Records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] =
+ * position, chains in selection order; T = n_sel * count samples, sample (k, r) is row r of chain k.  The rates are
+ * on the log scale as stored: manycd = 0: cd [n_sel][count][3], the (c, d, loglik) rows of
+ * sr_session_fetch_records (loglik is not read); manycd != 0: cd [n_sel][count][2M], c[M] then d[M], as
+ * sr_session_fetch_cd_vectors gives them.  No flip input: reflecting a chain (a' = N - b, b' = N - a,
+ * pi' = N - 1 - pi) leaves every alive bit, and so every output, unchanged.
+ * Term table, per sample (and per taxon when manycd): ec = exp(c), ed = exp(d) (this library's exp and log, bit
+ * for bit the C library's), p = {1.0 - ec, ed, 1.0 - ed, ec}, l = {log(1.0 - ec), d, log(1.0 - ed), c}; the
+ * indices: 0 true zero, 1 false zero, 2 true one, 3 false one.
+ * Cell (n, m) in sample (k, r): alive = a_m <= pi_n < b_m, compared in int32 (any int16 is legal, nothing is
+ * "outside"); with x = X[n][m] the index is 0 (x = 0, not alive), 1 (x = 0, alive), 2 (x = 1, alive), 3 (x = 1, not
+ * alive).
+ * Order of every sum over samples (part of the interface): within chain k sequentially over r ascending from +0.0,
+ * then the chain sums sequentially over k ascending from +0.0; no fma, no floating-point atomics.
+ * Pointwise, [N][M] f64: Sp the sum of the p terms, Sl of the l terms;
+ *   lppd      log(Sp / (double)T)
+ *   ll_mean   mu = Sl / (double)T
+ *   pwaic     V / (double)(T - 1), V the sum, in the same order, of (l - mu) * (l - mu)
+ * Reduction (plain C on the host; sr_waic_reduce runs it alone on given lppd, pwaic): e_i = lppd_i - pwaic_i;
+ * lppd_sum, p_waic, elpd the sequential row-major sums (n major) of lppd_i, pwaic_i, e_i from +0.0;
+ * waic = -2.0 * elpd; me = elpd / (double)(N M), Q the sequential sum of (e_i - me)^2,
+ * se = sqrt((double)(N M) * (Q / (double)(N M - 1))) (NaN when N M = 1); site_elpd[n] the sequential sum of e over m
+ * ascending, taxon_elpd[m] over n ascending; n_high the cells with pwaic_i > 0.4, the usual warning threshold.
+ * Every output pointer is optional (NULL = skip); the scalars are always written.
+ * SR_EINVAL: NULL ds, ab_pi, cd or out, n_sel <= 0, count < 1, T < 2, T >= 2^31, N outside 1..32767, M < 1, any c or
+ * d that is read outside [-700, -2^-50] or NaN (inside, every term is finite and every p > 0); the session form also
+ * for rows beyond the buffered records or a chain index out of range.  SR_EUNSUPPORTED: N M > 2^27, or a library
+ * built without the device layer.  All reported before any kernel runs, the outputs untouched.  Device scratch is
+ * bounded: chains and rows are taken in batches of at most SR_WAIC_SCRATCH bytes each (environment, default
+ * 256 MiB) of per-chain partial sums and of table rows; the results do not depend on it. */
+typedef struct {
+  double *lppd, *ll_mean, *pwaic;        /* out: [N][M] each, NULL = skip */
+  double *site_elpd, *taxon_elpd;        /* out: [N], [M], NULL = skip */
+  double elpd, se, p_waic, lppd_sum, waic;
+  int64_t n_high;
+  double kernel_ms;
+} sr_waic_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M and X */
+int sr_waic(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel,
+            int32_t count, int32_t device, sr_waic_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order), on the session's
+   stream; manycd is the session's; the session's state and records are left untouched */
+int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                    sr_waic_out *out);
+/* the reduction alone, on the host: scalars, site_elpd and taxon_elpd of out from lppd, pwaic [N][M] */
+int sr_waic_reduce(int32_t N, int32_t M, const double *lppd, const double *pwaic, sr_waic_out *out);
+
 const char *sr_strerror(int code);
 int sr_device_count(void);
 const char *sr_version(void);

@@ -1455,6 +1455,153 @@ SR_API int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_
   return post_rc(rc);
 }
 
+/* ---- WAIC and the pointwise model fit (definitions: include/seriation.h) ---- */
+/* sr_waic.hip's entry points, weak for the same reason as the moment kernels' */
+extern __typeof__(srw_waic_dev) srw_waic_dev __attribute__((weak));
+extern __typeof__(srw_waic_host) srw_waic_host __attribute__((weak));
+
+#define WAIC_CELLS_MAX ((int64_t)1 << 27)
+
+SR_API int sr_waic_reduce(int32_t N, int32_t M, const double *lppd, const double *pwaic, sr_waic_out *out)
+{
+  if (!lppd || !pwaic || !out || N < 1 || M < 1) return SR_EINVAL;
+  const int64_t nm = (int64_t)N * M;
+  double sl = 0.0, sp = 0.0, se = 0.0, Q = 0.0;
+  int64_t high = 0;
+  for (int64_t i = 0; i < nm; i++) {
+    const double e = lppd[i] - pwaic[i];
+    sl += lppd[i];
+    sp += pwaic[i];
+    se += e;
+    if (pwaic[i] > 0.4) high++;
+  }
+  const double me = se / (double)nm;
+  for (int64_t i = 0; i < nm; i++) {
+    const double dv = (lppd[i] - pwaic[i]) - me;
+    Q += dv * dv;
+  }
+  out->lppd_sum = sl;
+  out->p_waic = sp;
+  out->elpd = se;
+  out->waic = -2.0 * se;
+  out->se = sqrt((double)nm * (Q / (double)(nm - 1)));
+  out->n_high = high;
+  if (out->site_elpd)
+    for (int32_t n = 0; n < N; n++) {
+      double a = 0.0;
+      for (int32_t m = 0; m < M; m++) a += lppd[(int64_t)n * M + m] - pwaic[(int64_t)n * M + m];
+      out->site_elpd[n] = a;
+    }
+  if (out->taxon_elpd)
+    for (int32_t m = 0; m < M; m++) {
+      double a = 0.0;
+      for (int32_t n = 0; n < N; n++) a += lppd[(int64_t)n * M + m] - pwaic[(int64_t)n * M + m];
+      out->taxon_elpd[m] = a;
+    }
+  return SR_OK;
+}
+
+/* the argument checks both forms share, made before any device call */
+static int waic_check(const sr_waic_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (!out || n_sel <= 0 || count < 1 || (int64_t)n_sel * count < 2 || (int64_t)n_sel * count >= ((int64_t)1 << 31))
+    return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  return SR_OK;
+}
+
+/* every c, d that will be read lies in [-700, -2^-50] (NaN fails): rows [count][cdw], c at [m], d at [Mt + m] */
+static int waic_cd_ok(const double *cd, int32_t count, int cdw, int Mt)
+{
+  for (int64_t r = 0; r < count; r++)
+    for (int j = 0; j < 2 * Mt; j++) {
+      const double v = cd[r * cdw + j];
+      if (!(v >= -700.0 && v <= -0x1p-50)) return 0;
+    }
+  return 1;
+}
+
+/* the pointwise arrays the caller did not ask for are temporaries here: the reduction needs lppd and pwaic */
+static int waic_run(int N, int M, sr_waic_out *out, int dev_form, int device, void *stream, const int16_t *rec,
+                    const long long *off, long long W, const int16_t *ab_pi, int32_t n_sel, int32_t count,
+                    const uint8_t *X, const double *const *cd, int cdw, int manycd)
+{
+  const size_t nm = (size_t)N * M;
+  double *lp = out->lppd ? out->lppd : (double *)malloc(nm * sizeof(double));
+  double *pw = out->pwaic ? out->pwaic : (double *)malloc(nm * sizeof(double));
+  int rc = (lp && pw) ? SR_OK : SR_ENOMEM;
+  float ms = 0.0f;
+  if (!rc)
+    rc = post_rc(dev_form ? srw_waic_dev(device, stream, rec, off, n_sel, count, W, N, M, X, cd, cdw, manycd, lp,
+                                         out->ll_mean, pw, &ms)
+                          : srw_waic_host(device, ab_pi, n_sel, count, N, M, X, cd, cdw, manycd, lp, out->ll_mean, pw,
+                                          &ms));
+  if (!rc) {
+    rc = sr_waic_reduce(N, M, lp, pw, out);
+    out->kernel_ms = ms;
+  }
+  if (lp != out->lppd) free(lp);
+  if (pw != out->pwaic) free(pw);
+  return rc;
+}
+
+SR_API int sr_waic(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel,
+                   int32_t count, int32_t device, sr_waic_out *out)
+{
+  if (!ds || !ab_pi || !cd) return SR_EINVAL;
+  int rc = waic_check(out, n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!ds->X) return SR_EINVAL;
+  const int Mt = manycd ? ds->M : 1, cdw = manycd ? 2 * ds->M : 3;
+  if (!waic_cd_ok(cd, (int32_t)((int64_t)n_sel * count), cdw, Mt)) return SR_EINVAL;
+  if ((int64_t)ds->N * ds->M > WAIC_CELLS_MAX) return SR_EUNSUPPORTED;
+  if (!srw_waic_host) return SR_EUNSUPPORTED;
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  if (!rows) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) rows[k] = cd + (size_t)k * count * cdw;
+  rc = waic_run(ds->N, ds->M, out, 0, device, NULL, NULL, NULL, 0, ab_pi, n_sel, count, ds->X, rows, cdw, manycd != 0);
+  free(rows);
+  return rc;
+}
+
+SR_API int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                           sr_waic_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = waic_check(out, n_sel, count, s->ds.N, s->ds.M);
+  if (rc) return rc;
+  if (first < 0 || first > s->nrec || count > s->nrec - first) return SR_EINVAL;
+  for (int k = 0; k < n_sel; k++)
+    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  if ((int64_t)s->ds.N * s->ds.M > WAIC_CELLS_MAX) return SR_EUNSUPPORTED;
+  if (!srw_waic_dev) return SR_EUNSUPPORTED;
+  const int16_t *rec;
+  int cap, dev;
+  void *stream;
+  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
+  const int M = s->ds.M, manycd = s->opts.manycd != 0;
+  const int Mt = manycd ? M : 1, cdw = manycd ? 2 * M : 3;
+  const long long W = 2LL * M + s->ds.N;
+  /* the rates come to the host through the fetch entry points (the int16 rows stay in HBM): every chain's
+     per-taxon rows at once, or the chosen chains' (c, d, loglik) rows one chain at a time */
+  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  double *buf = (double *)malloc(sizeof(double) * (size_t)(manycd ? s->nchains : n_sel) * count * cdw);
+  rc = (off && rows && buf) ? SR_OK : SR_ENOMEM;
+  if (!rc && manycd && srk_fetch_cdv(s->dev, first, count, buf)) rc = SR_EDEVICE;
+  for (int k = 0; k < n_sel && !rc; k++) {
+    off[k] = ((long long)chains[k] * cap + first) * W;
+    rows[k] = buf + (size_t)(manycd ? chains[k] : k) * count * cdw;
+    if (!manycd && srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, (double *)rows[k])) rc = SR_EDEVICE;
+    if (!rc && !waic_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
+  }
+  if (!rc) rc = waic_run(s->ds.N, M, out, 1, dev, stream, rec, off, W, NULL, n_sel, count, s->ds.X, rows, cdw, manycd);
+  free(off);
+  free(rows);
+  free(buf);
+  return rc;
+}
+
 SR_API void sr_session_destroy(sr_session *s)
 {
   if (!s) return;

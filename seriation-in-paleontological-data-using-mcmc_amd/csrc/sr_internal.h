@@ -151,6 +151,18 @@ int srr_relations_dev(int device, void *stream, const int16_t *d_rec, const long
 int srr_relations_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *flip,
                        uint32_t *const pair[4], uint32_t *dur_hist, uint32_t *dur_outside, uint32_t *rich_hist,
                        float *ms);
+/* WAIC's pointwise terms (sr_waic.hip): lppd, ll_mean, pwaic [N][M] over n_sel chains' `count` rows, summed in the
+   order include/seriation.h fixes.  X [N][M] and cd [n_sel] are host inputs: chain k's c, d rows [count][cdw],
+   c of taxon m at [m], d at [Mt + m], Mt = M when manycd and 1 otherwise (cdw 3 takes the (c, d, loglik) rows as
+   they are), every value already checked against the domain; lppd, pwaic and the optional ll_mean are host
+   buffers.  Weak in sr_host.c like the relations' entry points: sr_waic returns SR_EUNSUPPORTED in the host-only
+   builds. */
+int srw_waic_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
+                 long long row_stride, int N, int M, const uint8_t *X, const double *const *cd, int cdw, int manycd,
+                 double *lppd, double *ll_mean, double *pwaic, float *ms);
+int srw_waic_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *X,
+                  const double *const *cd, int cdw, int manycd, double *lppd, double *ll_mean, double *pwaic,
+                  float *ms);
 void srk_destroy(srk_dev *d);
 
 #ifdef __cplusplus

@@ -7,7 +7,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
     python -m seriation_amd DATASET [--chains 100] [--burnin 1000] [--samples 1000] [--thin 10]
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
-                                    [--marginals] [--relations]
+                                    [--marginals] [--relations] [--waic]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -23,6 +23,10 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 mean and the 2.5 %, 50 % and 97.5 % quantiles of the number of taxa alive; Chains/taxon_pairs.csv:
                 per pair i < j the counts of samples in which i originates before j and j before i, i ends before
                 j and j before i, i is over before j begins and j before i begins, and the two coexist
+  --waic        with --select: WAIC and the pointwise fit of the chosen chains (analysis.waic_from_records over their
+                chain_data.csv, shared rates or, with --manycd, per-taxon rates).  Chains/waic.csv: one row
+                elpd_waic, se, p_waic, lppd, waic, n_high (cells with p_waic above 0.4), samples, cells;
+                Chains/waic_sites.csv and Chains/waic_taxa.csv: each site's and each taxon's share of elpd_waic
   --no-save     sample without writing files; prints one JSON summary per chain
   --rng         mt: GSL MT19937 as the reference (default); philox: the opt-in counter-based
                 Philox4x32-10 stream for sampling (statistically equivalent, not bit-equal)
@@ -83,6 +87,25 @@ def write_relations(ds, chains, root, device=0):
                                                           pr[j][i], ov[i][j]))
 
 
+def write_waic(ds, chains, root, manycd=False, device=0):
+    """Chains/waic.csv, Chains/waic_sites.csv and Chains/waic_taxa.csv of the chosen chains: WAIC over their
+    chain_data.csv rows, the rates read back from the files' c and d tokens."""
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    cd = analysis.read_chain_cd(root, chains, ds.M, manycd=manycd)
+    r = analysis.waic_from_records(ds, rec, cd, manycd=manycd, pointwise=False, device=device)
+    with open(os.path.join(root, "Chains", "waic.csv"), "w") as fh:
+        fh.write("elpd_waic,se,p_waic,lppd,waic,n_high,samples,cells\n")
+        fh.write("%r,%r,%r,%r,%r,%d,%d,%d\n" % (float(r["elpd_waic"]), float(r["se"]), float(r["p_waic"]),
+                                                float(r["lppd_sum"]), float(r["waic"]), r["n_high"], r["total"],
+                                                ds.N * ds.M))
+    for name, key, n in (("waic_sites.csv", "site", ds.N), ("waic_taxa.csv", "taxon", ds.M)):
+        with open(os.path.join(root, "Chains", name), "w") as fh:
+            fh.write("%s,elpd\n" % key)
+            for i in range(n):
+                fh.write("%d,%r\n" % (i, float(r[key + "_elpd"][i])))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m seriation_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("dataset")
@@ -100,7 +123,10 @@ def main(argv=None):
     ap.add_argument("--manycd", action="store_true")
     ap.add_argument("--marginals", action="store_true")
     ap.add_argument("--relations", action="store_true")
+    ap.add_argument("--waic", action="store_true")
     a = ap.parse_args(argv)
+    if a.waic and (a.select < 1 or a.no_save):
+        ap.error("--waic needs --select K (and the chain files: not with --no-save)")
     if a.marginals and (a.select < 1 or a.no_save):
         ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
     if a.relations and (a.select < 1 or a.no_save):
@@ -138,6 +164,8 @@ def main(argv=None):
                 write_marginals(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
             if a.relations:
                 write_relations(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
+            if a.waic:
+                write_waic(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, devices[0] if devices else 0)
     return 1 if any(s.get("consistent", 0) for s in summ) else 0
 
 

@@ -101,6 +101,16 @@ class sr_rel_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_waic_out(ctypes.Structure):
+    _fields_ = [("lppd", ctypes.POINTER(ctypes.c_double)), ("ll_mean", ctypes.POINTER(ctypes.c_double)),
+                ("pwaic", ctypes.POINTER(ctypes.c_double)),
+                ("site_elpd", ctypes.POINTER(ctypes.c_double)), ("taxon_elpd", ctypes.POINTER(ctypes.c_double)),
+                ("elpd", ctypes.c_double), ("se", ctypes.c_double), ("p_waic", ctypes.c_double),
+                ("lppd_sum", ctypes.c_double), ("waic", ctypes.c_double),
+                ("n_high", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                            ctypes.POINTER(sr_record))
 
@@ -117,7 +127,7 @@ PUBLIC_SYMBOLS = [
     "sr_session_checkpoint", "sr_session_restore",
     "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior",
     "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals",
-    "sr_relations", "sr_session_relations", "sr_strerror", "sr_device_count", "sr_version",
+    "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce", "sr_strerror", "sr_device_count", "sr_version",
 ]
 
 _LIB = None
@@ -184,6 +194,9 @@ def _lib():
         "sr_session_marginals": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_marg_out)]),
         "sr_relations": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_rel_out)]),
         "sr_session_relations": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_rel_out)]),
+        "sr_waic": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, c_i32, P(sr_waic_out)]),
+        "sr_session_waic": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_waic_out)]),
+        "sr_waic_reduce": (c_int, [c_i32, c_i32, P(c_double), P(c_double), P(sr_waic_out)]),
         "sr_strerror": (ctypes.c_char_p, [c_int]),
         "sr_device_count": (c_int, []),
         "sr_version": (ctypes.c_char_p, []),

@@ -406,6 +406,101 @@ def diversity_curve(rich_hist, probs=PROBS):
     return {"mean": num.astype(np.float64) / T.astype(np.float64), "quant": quant}
 
 
+# ---------------------------------------------------------------- WAIC and the pointwise model fit
+# Does the model fit, and which of the two models -- error rates shared by all taxa, or per-taxon rates (manycd) --
+# fits better: the widely applicable information criterion over the selected chains' samples, every output defined
+# to the bit (definitions: include/seriation.h).  The N M T reduction runs on the GPU (csrc/sr_waic.hip); there is no
+# CPU fallback.  No orientation is needed: a reflected chain gives the same alive bits.
+_WAIC_SCALARS = ("elpd", "se", "p_waic", "lppd_sum", "waic")
+
+
+def _waic_outs(N, M, pointwise):
+    arrs = {"site_elpd": np.zeros(N), "taxon_elpd": np.zeros(M)}
+    if pointwise:
+        arrs.update({k: np.zeros((N, M)) for k in ("lppd", "ll_mean", "pwaic")})
+    out = L.sr_waic_out()
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data_as(_DBLP))
+    return out, arrs
+
+
+def _waic_result(out, arrs, total, pointwise):
+    res = {k: getattr(out, k) for k in _WAIC_SCALARS}
+    res["elpd_waic"] = res.pop("elpd")   # "elpd" names the pointwise array below
+    res["n_high"] = int(out.n_high)
+    res["site_elpd"], res["taxon_elpd"] = arrs["site_elpd"], arrs["taxon_elpd"]
+    res["total"] = total
+    res["kernel_ms"] = out.kernel_ms
+    if pointwise:
+        for k in ("lppd", "ll_mean", "pwaic"):
+            res[k] = arrs[k]
+        res["elpd"] = arrs["lppd"] - arrs["pwaic"]
+    return res
+
+
+def waic_from_records(dataset, ab_pi, cd, manycd=False, pointwise=True, device=0):
+    """sr_waic: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order) and the rates on the log
+    scale, cd [n_sel][count][3] ((c, d, loglik) rows as Session.fetch_records gives them) or, manycd, [n_sel][count][2M]
+    (c[M] then d[M], as Session.fetch_cd_vectors) -> {"elpd_waic", "se", "p_waic", "lppd_sum", "waic" (floats),
+    "n_high", "site_elpd" [N], "taxon_elpd" [M], "total" (the number of samples), "kernel_ms"}; pointwise adds
+    "lppd", "ll_mean", "pwaic" and "elpd" = lppd - pwaic, [N][M] each."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    r = np.ascontiguousarray(cd, dtype=np.float64)
+    assert r.shape == (n_sel, count, 2 * dataset.M if manycd else 3)
+    out, arrs = _waic_outs(dataset.N, dataset.M, pointwise)
+    _check(L.lib().sr_waic(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)),
+                           r.ctypes.data_as(_DBLP), int(bool(manycd)), n_sel, count, device, ctypes.byref(out)),
+           "sr_waic")
+    return _waic_result(out, arrs, n_sel * count, pointwise)
+
+
+def waic_from_session(session, chains, first=0, count=None, pointwise=True):
+    """sr_session_waic: the same over a session's records still in HBM, rows [first, first + count) of chains
+    (session chain indices in selection order); shared or per-taxon rates as the session samples them."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs = _waic_outs(session.ds.N, session.ds.M, pointwise)
+    _check(L.lib().sr_session_waic(session.h, ch, len(chains), first, count, ctypes.byref(out)), "sr_session_waic")
+    return _waic_result(out, arrs, len(chains) * count, pointwise)
+
+
+def waic_compare(a, b):
+    """Two WAIC results with pointwise arrays of equal shape (one dataset, e.g. shared rates against manycd) ->
+    {"elpd_diff": the sequential row-major sum of a.elpd_i - b.elpd_i (positive: a fits better), "se_diff":
+    sqrt(n * (Q / (n - 1))), Q the sequential sum of (diff_i - elpd_diff / n)^2, n the number of cells (NaN when
+    n = 1)}: sr_waic_reduce's two-pass formula on the differences, host numpy."""
+    ea, eb = np.asarray(a["elpd"], np.float64), np.asarray(b["elpd"], np.float64)
+    assert ea.shape == eb.shape and ea.size >= 1
+    d = (ea - eb).reshape(-1)
+    n = float(d.size)
+    tot = np.cumsum(d)[-1]
+    dev = d - tot / n
+    q = np.cumsum(dev * dev)[-1]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        se = np.sqrt(np.float64(n) * (q / np.float64(n - 1.0)))
+    return {"elpd_diff": float(tot), "se_diff": float(se)}
+
+
+def read_chain_cd(root, chains, taxa, manycd=False):
+    """chain_data.csv of each chain -> the rates on the log scale, c = math.log(float(token)) of fields 3 and 4:
+    float64 [n][lines][3] (the first c and d token and field 5, the line's loglik) or, manycd, [n][lines][2M] (all M
+    c tokens, then all M d tokens).  All chains must hold the same number of lines."""
+    out = []
+    for chain in chains:
+        rows = []
+        for line in _chain_lines(root, chain):
+            f = line.split(",")
+            c, d = f[3].split()[:taxa], f[4].split()[:taxa]
+            if manycd:
+                rows.append([math.log(float(t)) for t in c] + [math.log(float(t)) for t in d])
+            else:
+                rows.append([math.log(float(c[0])), math.log(float(d[0])), float(f[5])])
+        out.append(np.array(rows, np.float64).reshape(len(rows), 2 * taxa if manycd else 3))
+    return np.stack(out)
+
+
 def read_chain_rows(root, chains, sites, taxa):
     """chain_data.csv of each chain -> int16 [n][lines][2M+N] (fields 0, 1, 2 tokens as the script
     slices them).  All chains must hold the same number of lines."""
