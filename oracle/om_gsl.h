@@ -177,10 +177,35 @@ static inline uint32_t om_rng_get(om_rng *r)
 
 static inline double om_uniform(om_rng *r) { return om_rng_get(r) / 4294967296.0; }
 
+/* Diagnostics beside ndraw (thread-local, never read by the sampler): how often the stream took one of the rare
+ * branches below.  tests/test_stream_inject_host.py and tests/test_gpu_stream_inject.py assert from them that the
+ * words they inject reach every branch (oracle_run_chain_mt zeroes and returns them). */
+enum {
+  OM_EV_UINT_CALLS, OM_EV_UINT_REJECT,   /* gsl_rng_uniform_int: calls, rejected words (k >= n) */
+  OM_EV_UPOS_CALLS, OM_EV_UPOS_RETRY,    /* gsl_rng_uniform_pos: calls, zero words drawn again */
+  OM_EV_ZIG_WEDGE, OM_EV_ZIG_TAIL, OM_EV_ZIG_REJECT,   /* ziggurat: outside the box in a strip, in the tail; y test failed */
+  OM_EV_GAMMA_VNEG, OM_EV_GAMMA_REJECT,  /* gamma: v <= 0; squeeze and log test both failed */
+  OM_EV_JOHNK,                           /* gsl_ran_beta calls that took Johnk's branch */
+  OM_EV_N
+};
+static __thread unsigned long long om_ev[OM_EV_N];
+
+/* Sensitivity control of tests/test_stream_inject_host.py ONLY (oracle_run_chain_mt's flag; nothing else sets it):
+ * answer as a precomputed table entry would if its "no rejection" bit were ignored -- uniform_int clamps a rejected
+ * quotient to n - 1 instead of drawing again, uniform_pos passes a zero through, the ziggurat takes every word as
+ * inside the box.  The events are still counted. */
+static __thread int om_ok_ignored;
+
 static inline double om_uniform_pos(om_rng *r)
 {
   double x;
-  do { x = om_uniform(r); } while (x == 0);
+  om_ev[OM_EV_UPOS_CALLS]++;
+  for (;;) {
+    x = om_uniform(r);
+    if (x != 0) break;
+    om_ev[OM_EV_UPOS_RETRY]++;
+    if (om_ok_ignored) break;
+  }
   return x;
 }
 
@@ -188,7 +213,13 @@ static inline unsigned long om_uniform_int(om_rng *r, unsigned long n)
 {
   unsigned long scale = 0xffffffffUL / n;
   unsigned long k;
-  do { k = om_rng_get(r) / scale; } while (k >= n);
+  om_ev[OM_EV_UINT_CALLS]++;
+  for (;;) {
+    k = om_rng_get(r) / scale;
+    if (k < n) break;
+    om_ev[OM_EV_UINT_REJECT]++;
+    if (om_ok_ignored) { k = n - 1; break; }
+  }
   return k;
 }
 
@@ -232,6 +263,8 @@ static inline double om_gaussian_ziggurat(om_rng *r, double sigma)
     i &= 0x7f;
     x = j * om_zig_wtab[i];
     if (j < om_zig_ktab[i]) break;
+    om_ev[i < 127 ? OM_EV_ZIG_WEDGE : OM_EV_ZIG_TAIL]++;
+    if (om_ok_ignored) break;
     if (i < 127) {
       double y0 = om_zig_ytab[i], y1 = om_zig_ytab[i + 1];
       double U1 = om_uniform(r);
@@ -243,6 +276,7 @@ static inline double om_gaussian_ziggurat(om_rng *r, double sigma)
       y = om_exp(-OM_ZIG_R * (x - 0.5 * OM_ZIG_R)) * U2;
     }
     if (y < om_exp(-0.5 * x * x)) break;
+    om_ev[OM_EV_ZIG_REJECT]++;
   }
   return sign * sigma * x;
 }
@@ -260,14 +294,17 @@ static inline double om_gamma(om_rng *r, double a, double b)
   double d = a - 1.0 / 3.0;
   double c = (1.0 / 3.0) / __builtin_sqrt(d);
   for (;;) {
-    do {
+    for (;;) {
       x = om_gaussian_ziggurat(r, 1.0);
       v = 1.0 + c * x;
-    } while (v <= 0);
+      if (!(v <= 0)) break;
+      om_ev[OM_EV_GAMMA_VNEG]++;
+    }
     v = v * v * v;
     u = om_uniform_pos(r);
     if (u < 1 - 0.0331 * x * x * x * x) break;
     if (om_log(u) < 0.5 * x * x + d * (1 - v + om_log(v))) break;
+    om_ev[OM_EV_GAMMA_REJECT]++;
   }
   return b * d * v;
 }
@@ -280,6 +317,7 @@ static inline double om_gamma(om_rng *r, double a, double b)
 static inline double om_beta(om_rng *r, double a, double b)
 {
   if (a <= 1.0 && b <= 1.0) {
+    om_ev[OM_EV_JOHNK]++;
     for (;;) {
       const double U = om_uniform_pos(r), V = om_uniform_pos(r);
       const double X = (a == 1.0) ? U : pow(U, 1.0 / a), Y = (b == 1.0) ? V : pow(V, 1.0 / b);

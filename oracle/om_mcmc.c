@@ -809,6 +809,60 @@ OM_API int oracle_run_chain_v(const char *text, long len, int maxs, unsigned lon
   return bad ? 1 : 0;
 }
 
+/*
+ * A chain started from an explicit MT19937 state (the stream-injection tests: tests/stream_inject.py).  Reads the
+ * model, seeds and randomizes as oracle_run_chain_v does; mt_after / mti_after (optional) receive the generator's
+ * 624 raw words and cursor as they stand there.  Then, when mt is given, x.rng.mt[0..623] = mt and x.rng.mti = mti
+ * (0..624); ndraw and the event counters of om_gsl.h are zeroed; ts saved calls of `sweeps` sweeps follow.
+ *   rec_int, rec_dbl, rec_cdv, acc_out: as oracle_run_chain_v; rng_words: words drawn by the ts calls;
+ *   events (optional): OM_EV_N counts over the ts calls.
+ *   ok_ignored: om_gsl.h's om_ok_ignored for this run -- the sensitivity control only.
+ * Returns 0, a parse error (< 0), -1 for a cursor outside 0..624, or 1 if the final consistency test failed.
+ */
+OM_API int oracle_run_chain_mt(const char *text, long len, int maxs, unsigned long seed, int manycd,
+                               const uint32_t *mt, int mti, int ts, int sweeps, int ok_ignored,
+                               int32_t *rec_int, double *rec_dbl, double *rec_cdv, long long *acc_out,
+                               unsigned long long *rng_words, uint32_t *mt_after, int *mti_after,
+                               unsigned long long *events)
+{
+  om_model x;
+  if (mt && (mti < 0 || mti > OM_MT_N)) return -1;
+  int rc = om_readmodel(&x, text, (size_t)len, maxs, manycd);
+  if (rc) return rc;
+  om_rng_seed(&x.rng, seed);
+  om_randomize(&x);
+  if (mt_after) memcpy(mt_after, x.rng.mt, sizeof(x.rng.mt));
+  if (mti_after) *mti_after = x.rng.mti;
+  if (mt) {
+    memcpy(x.rng.mt, mt, sizeof(x.rng.mt));
+    x.rng.mti = mti;
+  }
+  x.rng.ndraw = 0;
+  memset(om_ev, 0, sizeof(om_ev));
+  om_ok_ignored = ok_ignored != 0;
+  const int N = x.N, M = x.M, W = 2 * M + N;
+  for (int i = 0; i < ts; i++) {
+    om_sample(&x, sweeps);
+    if (rec_int) {
+      int32_t *r = rec_int + (size_t)i * W;
+      for (int m = 0; m < M; m++) { r[m] = x.a[m]; r[M + m] = x.b[m]; }
+      for (int n = 0; n < N; n++) r[2 * M + n] = x.pi[n];
+    }
+    if (rec_dbl) { rec_dbl[3 * i] = x.c[0]; rec_dbl[3 * i + 1] = x.d[0]; rec_dbl[3 * i + 2] = x.loglik; }
+    if (rec_cdv) {
+      memcpy(rec_cdv + (size_t)i * 2 * M, x.c, (size_t)M * sizeof(double));
+      memcpy(rec_cdv + (size_t)i * 2 * M + M, x.d, (size_t)M * sizeof(double));
+    }
+  }
+  om_ok_ignored = 0;
+  if (acc_out) memcpy(acc_out, x.acc, sizeof(x.acc));
+  if (rng_words) *rng_words = x.rng.ndraw;
+  if (events) memcpy(events, om_ev, sizeof(om_ev));
+  const int bad = om_consistent(&x, 1, 0);
+  om_free(&x);
+  return bad ? 1 : 0;
+}
+
 /* ---- references of the device certification self-tests (tests/test_gpu_cert.py) ----
  * oracle_auxa_pick: mcmc_auxa + mcmc_logtop + mcmc_randompick (mcmc.c:828-915) over walk-order bits x[0..b) from
  * limit a, with the uniform u given instead of drawn; returns the pick, p_out (optional, b + 1) the probabilities

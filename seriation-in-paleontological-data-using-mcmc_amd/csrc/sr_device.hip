@@ -386,50 +386,6 @@ __device__ __forceinline__ double rng_uniform_pos(DRng &r, int t, int nthr)
   return x;
 }
 
-template <bool WAVE>
-__device__ __forceinline__ uint32_t rng_uniform_int(DRng &r, uint32_t n, int t, int nthr)
-{
-  uint32_t scale = 0xffffffffu / n, k;
-  do { k = rng_get<WAVE>(r, t, nthr) / scale; } while (k >= n);
-  return k;
-}
-
-/* gsl_rng_uniform_int(n) with its divisor scale = 0xffffffff/n precomputed; the quotient
- * get()/scale is taken from a double reciprocal and corrected to the exact integer. */
-struct UDiv { uint32_t n, scale; double rs; };
-__device__ __forceinline__ UDiv make_udiv(uint32_t n)
-{
-  UDiv u;
-  u.n = n;
-  u.scale = 0xffffffffu / n;
-  u.rs = 1.0 / (double)u.scale;
-  return u;
-}
-template <bool WAVE>
-__device__ __forceinline__ uint32_t rng_uint_fast(DRng &r, const UDiv &u, int t, int nthr)
-{
-  uint32_t k;
-  do {
-    const uint32_t g = rng_get<WAVE>(r, t, nthr);
-    uint32_t q = (uint32_t)((double)g * u.rs);
-    const uint64_t qs = (uint64_t)q * u.scale;
-    if (qs > g) q--;
-    else if (g - (uint32_t)qs >= u.scale) q++;
-    k = q;
-  } while (k >= u.n);
-  return k;
-}
-
-/* quotient get()/scale of gsl_rng_uniform_int for a tempered word g (k >= n means GSL rejects g) */
-__device__ __forceinline__ uint32_t udiv_word(uint32_t g, const UDiv &u)
-{
-  uint32_t q = (uint32_t)((double)g * u.rs);
-  const uint64_t qs = (uint64_t)q * u.scale;
-  if (qs > g) q--;
-  else if (g - (uint32_t)qs >= u.scale) q++;
-  return q;
-}
-
 /* gsl_rng_uniform_int's quotient g / scale by an invariant-divisor multiply (Hacker's Delight
  * round-up method, exact for every 32-bit g; scale >= 2 here since n <= 4095): scalar ALU only */
 struct UDivM { uint32_t n, m; int l; };
@@ -3961,6 +3917,40 @@ extern "C" __attribute__((visibility("default"))) int sr_device_selftest_math(in
   HIPCHK(hipMemcpy(out_log, dl, n * 8, hipMemcpyDeviceToHost));
   (void)hipFree(din); (void)hipFree(de); (void)hipFree(dl);
   return 0;
+}
+
+/* The sweep kernel's divider on caller-chosen words: q[k] = g[k] / (0xffffffff / n[k]) as make_udivm + udivm
+ * compute it (even k) and as udivm_v does (odd k; the same expression over the unpacked magic number, phase C's
+ * form).  tests/test_gpu_stream_inject.py sends every divisor 1..4095 with the words around every multiple of its
+ * scale.  -1: a divisor outside 1..4095 (the sampler's domain, N <= 4095), refused before any device call. */
+__global__ void sr_udiv_selftest_kernel(const uint32_t *n, const uint32_t *g, long count, uint32_t *q)
+{
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) {
+    const UDivM u = make_udivm(n[i]);
+    q[i] = (i & 1) ? udivm_v(g[i], u.m, u.l) : udivm(g[i], u);
+  }
+}
+
+extern "C" __attribute__((visibility("default"))) int sr_device_selftest_udiv(int device, const uint32_t *n,
+                                                                             const uint32_t *g, long count, uint32_t *q)
+{
+  if (count <= 0) return 0;
+  if (!n || !g || !q) return -1;
+  for (long k = 0; k < count; ++k)
+    if (n[k] < 1 || n[k] > 4095) return -1;
+  HIPCHK(hipSetDevice(device));
+  uint32_t *dn = nullptr, *dg = nullptr, *dq = nullptr;
+  int rc = hipMalloc(&dn, count * 4) != hipSuccess || hipMalloc(&dg, count * 4) != hipSuccess ||
+           hipMalloc(&dq, count * 4) != hipSuccess;
+  if (!rc) rc = hipMemcpy(dn, n, count * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(dg, g, count * 4, hipMemcpyHostToDevice) != hipSuccess;
+  if (!rc) {
+    hipLaunchKernelGGL(sr_udiv_selftest_kernel, dim3(1024), dim3(256), 0, 0, dn, dg, count, dq);
+    rc = hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess;
+  }
+  if (!rc) rc = hipMemcpy(q, dq, count * 4, hipMemcpyDeviceToHost) != hipSuccess;
+  (void)hipFree(dn); (void)hipFree(dg); (void)hipFree(dq);
+  return rc ? -2 : 0;
 }
 
 /* ================================================================ certification self-tests (test hooks)

@@ -215,6 +215,8 @@ def _lib():
         "sr_session_spec_embedded": (c_i32, [c_void_p]),
         "sr_spec_is_embedded": (c_int, [c_int, c_int, c_int, c_int]),
         "sr_device_selftest_math": (c_int, [c_int, P(c_double), ctypes.c_long, P(c_double), P(c_double)]),
+        "sr_device_selftest_udiv": (c_int, [c_int, P(ctypes.c_uint32), P(ctypes.c_uint32), ctypes.c_long,
+                                            P(ctypes.c_uint32)]),
     }
     for name, (res, args) in sig.items():
         if not hasattr(L, name):   # an older build (A/B variants); tests/test_abi.py checks the product's exports

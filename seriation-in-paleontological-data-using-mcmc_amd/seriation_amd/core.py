@@ -146,13 +146,14 @@ class Session:
 
     @classmethod
     def restore(cls, dataset, path, device=0, sweeps_per_call=10, calls_per_launch=0, block_threads=0,
-                columns="auto", rng="mt", manycd=0):
+                columns="auto", rng="mt", generic=False, manycd=0):
         """sr_session_restore: a session continuing the chains of a checkpoint over `dataset` (manycd must
-        name the checkpoint's kind)."""
+        name the checkpoint's kind; generic as in Session)."""
         self = cls.__new__(cls)
         self.ds = dataset
         self.opts = make_opts(sweeps_per_call=sweeps_per_call, device=device, block_threads=block_threads,
-                              calls_per_launch=calls_per_launch, columns=columns, rng=rng, manycd=manycd)
+                              calls_per_launch=calls_per_launch, columns=columns, rng=rng, generic=generic,
+                              manycd=manycd)
         h = ctypes.c_void_p()
         _check(L.lib().sr_session_restore(ctypes.byref(dataset.c), os.fsencode(path), ctypes.byref(self.opts),
                                           ctypes.byref(h)), "sr_session_restore")

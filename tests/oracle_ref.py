@@ -46,6 +46,11 @@ def load(path):
                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      P(ctypes.c_int32), P(ctypes.c_double), P(ctypes.c_int32), P(ctypes.c_double),
                                      P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_longlong), P(ctypes.c_ulonglong)]
+    L.oracle_run_chain_mt.restype = ctypes.c_int
+    L.oracle_run_chain_mt.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_int, ctypes.c_ulong, ctypes.c_int,
+                                      P(ctypes.c_uint32), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      P(ctypes.c_int32), P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_longlong),
+                                      P(ctypes.c_ulonglong), P(ctypes.c_uint32), P(ctypes.c_int), P(ctypes.c_ulonglong)]
     L.oracle_auxa_pick.restype = ctypes.c_int
     L.oracle_auxa_pick.argtypes = [P(ctypes.c_int32), ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, P(ctypes.c_double)]
@@ -122,6 +127,47 @@ def run_chain(text, seed, tb, ts, sweeps=10, check=0, maxs=2000, want_init=False
                burnin_s=float(ph[0]), sample_s=float(ph[1]))
     if manycd:
         out["rec_cdv"] = cv[:ts * 2 * M].reshape(ts, 2 * M)
+    return out
+
+
+# om_gsl.h's event counters, in the order of its OM_EV_* enum
+EVENTS = ("uint_calls", "uint_reject", "upos_calls", "upos_retry", "zig_wedge", "zig_tail", "zig_reject",
+          "gamma_vneg", "gamma_reject", "johnk")
+
+
+def run_chain_mt(text, seed, mt=None, mti=0, ts=1, sweeps=2, maxs=0, manycd=0, shape=None, ok_ignored=False):
+    """oracle_run_chain_mt: the chain of `seed` after mcmc_randomize, continued from the MT19937 state (mt: 624 raw
+    words, mti: cursor) when one is given, for ts saved calls of `sweeps` sweeps.  Returns dict(rc, rec_int [ts, 2M+N],
+    rec_dbl [ts, 3], rec_cdv [ts, 2M] for manycd, acc [7], words (drawn by the ts calls), mt0 / mti0 (the state after
+    randomize, before mt replaced it), ev (EVENTS counts over the ts calls)).  shape = (N, M) spares the parse.
+    ok_ignored: the sensitivity control of tests/test_stream_inject_host.py, nothing else."""
+    if isinstance(text, str):
+        text = text.encode()
+    if shape is None:
+        rc, X, _ = parse(text, maxs)
+        assert rc == 0, rc
+        shape = X.shape
+    N, M = shape
+    W = 2 * M + N
+    ri = np.zeros((ts, W), np.int32)
+    rd = np.zeros((ts, 3))
+    cv = np.zeros((ts, 2 * M)) if manycd else None
+    acc = np.zeros(7, np.int64)
+    words = ctypes.c_ulonglong()
+    mt0 = np.zeros(624, np.uint32)
+    mti0 = ctypes.c_int()
+    ev = np.zeros(len(EVENTS), np.uint64)
+    if mt is not None:
+        mt = np.ascontiguousarray(mt, np.uint32)
+        assert mt.shape == (624,)
+    rc = lib().oracle_run_chain_mt(text, len(text), maxs, seed, 1 if manycd else 0, _p(mt, ctypes.c_uint32), mti, ts,
+                                   sweeps, 1 if ok_ignored else 0, _p(ri, ctypes.c_int32), _p(rd, ctypes.c_double),
+                                   _p(cv, ctypes.c_double), _p(acc, ctypes.c_longlong), ctypes.byref(words),
+                                   _p(mt0, ctypes.c_uint32), ctypes.byref(mti0), _p(ev, ctypes.c_ulonglong))
+    out = dict(rc=rc, rec_int=ri, rec_dbl=rd, acc=acc, words=words.value, mt0=mt0, mti0=mti0.value,
+               ev=dict(zip(EVENTS, (int(v) for v in ev))))
+    if manycd:
+        out["rec_cdv"] = cv
     return out
 
 

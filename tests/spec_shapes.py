@@ -20,7 +20,8 @@ def shapes():
     out |= {(spec[0], spec[1], spec[2], 0) for _, spec, _ in test_gpu_jit.CASES if spec is not None}
     out |= {(256, 300, 5, 0), (400, 150, 5, 0),   # test_gpu_edge.test_steep_walks
             (70, 90, 3, 0), (70, 90, 9, 0),      # test_gpu_jit shards, test_gpu_multi
-            (40, 24, 3, 0)}                      # test_gpu_edge.test_johnk_beta_branch
+            (40, 24, 3, 0),                      # test_gpu_edge.test_johnk_beta_branch, test_gpu_stream_inject
+            (300, 12, 9, 0), (300, 12, 33, 0), (560, 12, 5, 0)}   # test_gpu_stream_inject (17-word walk, nh > 32, LDS walk)
     import ref_exec
     out |= {(src["N"], src["M"], src["nh"], 0) for _, src, _, _, _ in ref_exec.FIXTURE_CASES   # test_gpu_reference_exec
             if not isinstance(src, str)}

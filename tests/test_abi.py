@@ -150,14 +150,9 @@ def test_restore_validates_chain_state(tmp_path):
     trunc = tmp_path / "trunc.srck"
     trunc.write_bytes(raw7[:-8])
     assert restore(trunc) == -2
-    N, M, nh, NW = ds.N, ds.M, ds.nh, (ds.N + 31) // 32
-    off = 40 + C * ctypes.sizeof(L.sr_chain_spec)
-    sizes = [("P", C * NW * M * 4), ("rpi", C * N * 4), ("hp", C * 64 * 4), ("ab", C * 2 * M * 4),
-             ("cnt", C * 4 * M * 4), ("cdl", C * 4 * 8), ("mt", C * 8 * 624 * 4), ("rng", C * 2 * 8), ("acc", C * 10 * 8)]
-    base = {}
-    for name, n in sizes:
-        base[name] = off
-        off += n
+    N, M, nh = ds.N, ds.M, ds.nh
+    from stream_inject import ck_layout   # the part offsets of the file (one copy, shared with the injection tests)
+    base, off = ck_layout(N, M, nh, C)
     raw = good.read_bytes()
     assert len(raw) == off
 
@@ -240,10 +235,11 @@ def test_checkpoint_many_hard_sites(tmp_path):
     if rc == 0:
         L.lib().sr_session_destroy(h)
     assert rc in (0, L.SR_EDEVICE)
-    NW = (N + 31) // 32
-    off = 40 + C * ctypes.sizeof(L.sr_chain_spec) + C * NW * M * 4 + C * N * 4
+    from stream_inject import ck_layout, nhcap
+    base, end = ck_layout(N, M, nh, C)
+    off = base["hp"]
     raw = bytearray(good.read_bytes())
-    assert len(raw) == off + C * 128 * 4 + C * 2 * M * 4 + C * 4 * M * 4 + C * 4 * 8 + C * 8 * 624 * 4 + C * 2 * 8 + C * 10 * 8
+    assert nhcap(nh) == 128 and base["ab"] - off == C * 128 * 4 and len(raw) == end
     hp = np.frombuffer(bytes(raw), "<i4", C * 128, off).reshape(C, 128)
     assert (np.diff(hp[0, :nh]) > 0).all() and (hp[:, nh:] == 0).all()
     raw[off + 4 * 80: off + 4 * 81] = np.array([N + 9], "<i4").tobytes()
