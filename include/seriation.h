@@ -413,6 +413,62 @@ int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t
 /* the reduction alone, on the host: scalars, site_elpd and taxon_elpd of out from lppd, pwaic [N][M] */
 int sr_waic_reduce(int32_t N, int32_t M, const double *lppd, const double *pwaic, sr_waic_out *out);
 
+/* ---- chain agreement: pairwise order distances between chains and mode clustering: exact integers ----
+ * (an extension: the reference's choose_chains ranks chains by mean -loglik and never asks whether they sampled the
+ * same order.)  Records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position; only the pi part is
+ * read.  Chains in selection order, chain k has `count` rows.  Any int16 value is legal: values are only compared,
+ * so nothing wraps and nothing is "outside".
+ *   pair_counts [n_sel][N][N] uint32   O_k[i][j]: the number of chain k's rows with pi_i < pi_j, all ordered i != j;
+ *                                      the diagonal is 0; for permutation rows O_k[i][j] + O_k[j][i] = count
+ *   dist [n_sel][n_sel] int64          dist[k][l] = sum over i < j of |O_k[i][j] - O_l[i][j]|
+ *   dist_mirror [n_sel][n_sel] int64   dist_mirror[k][l] = sum over i < j of |O_k[i][j] - O_l[j][i]|: the distance
+ *                                      from chain k to the reflection of chain l (pi' = N - 1 - pi); the diagonal is
+ *                                      defined: how far a chain is from its own mirror image
+ *   scale = count * N (N - 1) / 2      the largest possible value: dist / scale lies in [0, 1]
+ * Exact integers: the result does not depend on the order of the adds.  count < 2^31 and fewer than 2^29 pairs, so
+ * every sum is below 2^60.  N = 1 is valid: no pairs, every distance 0, scale 0.  Every output pointer is optional
+ * (NULL = skip); scale and kernel_ms are always written.
+ * sr_agreement_distances is the reduction alone, from pair counts in host memory (any uint32 values; e.g. matrices
+ * gathered from several GPUs).
+ * SR_EINVAL: NULL ds, ab_pi, out or pair_counts (the input of sr_agreement_distances), n_sel <= 0, count < 1,
+ * n_sel * count >= 2^31, N outside 1..32767; the session form also for rows beyond the buffered records or a chain
+ * index out of range.  SR_EUNSUPPORTED: n_sel > 4096, a requested pair_counts larger than 2^28 entries, or a library
+ * built without the device layer.  All reported before any device call, the outputs untouched.  Device scratch is
+ * bounded: the site pairs are taken in bands of at most SR_AGREE_SCRATCH bytes of per-chain counts (environment,
+ * read at each call, default 256 MiB; one row of 64-site tiles at least); the results do not depend on it.
+ *
+ * Mode clustering (sr_agreement_modes: host only, plain C, no GPU) over n chains:
+ *   1. for k < l, e = min(dist[k][l], dist_mirror[k][l]); only the upper triangle is read;
+ *   2. k and l are linked iff (double)e <= threshold * (double)scale: one f64 multiply and one compare;
+ *   3. modes are the connected components, numbered from 0 in ascending order of their smallest chain index;
+ *   4. flips: the smallest chain of a component has flip 0; breadth-first from it (a first-in first-out queue, the
+ *      neighbours of each entry tried in ascending chain index), a chain l first reached from k gets
+ *      flip[l] = flip[k] ^ (dist_mirror[min(k,l)][max(k,l)] < dist[min(k,l)][max(k,l)]);
+ *   5. medoid[g]: the member of mode g with the smallest sum of e to the other members, ties to the lowest index;
+ *   6. size[g]: the number of members.
+ * mode [n] is required; flip [n], medoid [n], size [n] (the first n_modes entries are written) and n_modes are
+ * optional.  SR_EINVAL: threshold outside [0, 1] or NaN, scale < 0, n <= 0, NULL dist, dist_mirror or mode. */
+typedef struct {
+  uint32_t *pair_counts;          /* out: [n_sel][N][N], NULL = skip */
+  int64_t *dist, *dist_mirror;    /* out: [n_sel][n_sel], NULL = skip */
+  int64_t scale;                  /* out */
+  double kernel_ms;               /* out */
+} sr_agree_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M */
+int sr_agreement(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                 sr_agree_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order), on the session's
+   stream; the session's state and records are left untouched */
+int sr_session_agreement(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                         sr_agree_out *out);
+/* the reduction alone, from pair counts in host memory (any uint32 values): e.g. matrices gathered from several GPUs */
+int sr_agreement_distances(int32_t N, int32_t n_sel, const uint32_t *pair_counts, int32_t device, int64_t *dist,
+                           int64_t *dist_mirror, double *kernel_ms);
+/* host only */
+int sr_agreement_modes(int32_t n, const int64_t *dist, const int64_t *dist_mirror, int64_t scale, double threshold,
+                       int32_t *mode, uint8_t *flip, int32_t *medoid, int32_t *size, int32_t *n_modes);
+
 const char *sr_strerror(int code);
 int sr_device_count(void);
 const char *sr_version(void);

@@ -1455,6 +1455,144 @@ SR_API int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_
   return post_rc(rc);
 }
 
+/* ---- chain agreement: pairwise order distances and mode clustering (definitions: include/seriation.h) ---- */
+/* sr_agree.hip's entry points, weak for the same reason as the moment kernels' */
+extern __typeof__(sra_agreement_dev) sra_agreement_dev __attribute__((weak));
+extern __typeof__(sra_agreement_host) sra_agreement_host __attribute__((weak));
+extern __typeof__(sra_distances_host) sra_distances_host __attribute__((weak));
+
+#define AGREE_CHAINS_MAX 4096
+
+/* the argument checks both forms share, made before any device call */
+static int agree_check(const sr_agree_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (!out || n_sel <= 0 || count < 1 || (int64_t)n_sel * count >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  if (n_sel > AGREE_CHAINS_MAX) return SR_EUNSUPPORTED;
+  if (out->pair_counts && (int64_t)n_sel * N * N > REL_OUT_MAX) return SR_EUNSUPPORTED;
+  return SR_OK;
+}
+
+static void agree_done(sr_agree_out *out, int32_t count, int32_t N, float ms)
+{
+  out->scale = (int64_t)count * ((int64_t)N * (N - 1) / 2);
+  out->kernel_ms = ms;
+}
+
+SR_API int sr_agreement(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                        sr_agree_out *out)
+{
+  if (!ds || !ab_pi) return SR_EINVAL;
+  int rc = agree_check(out, n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!sra_agreement_host) return SR_EUNSUPPORTED;
+  float ms = 0.0f;
+  rc = sra_agreement_host(device, ab_pi, n_sel, count, ds->N, ds->M, out->pair_counts, (long long *)out->dist,
+                          (long long *)out->dist_mirror, &ms);
+  if (!rc) agree_done(out, count, ds->N, ms);
+  return post_rc(rc);
+}
+
+SR_API int sr_session_agreement(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                sr_agree_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = agree_check(out, n_sel, count, s->ds.N, s->ds.M);
+  if (rc == SR_EINVAL) return rc;
+  if (first < 0 || first > s->nrec || count > s->nrec - first) return SR_EINVAL;
+  for (int k = 0; k < n_sel; k++)
+    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  if (rc) return rc;
+  if (!sra_agreement_dev) return SR_EUNSUPPORTED;
+  const int16_t *rec;
+  int cap, dev;
+  void *stream;
+  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
+  const long long W = 2LL * s->ds.M + s->ds.N;
+  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
+  if (!off) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
+  float ms = 0.0f;
+  rc = sra_agreement_dev(dev, stream, rec, off, n_sel, count, W, s->ds.N, s->ds.M, out->pair_counts,
+                         (long long *)out->dist, (long long *)out->dist_mirror, &ms);
+  if (!rc) agree_done(out, count, s->ds.N, ms);
+  free(off);
+  return post_rc(rc);
+}
+
+SR_API int sr_agreement_distances(int32_t N, int32_t n_sel, const uint32_t *pair_counts, int32_t device, int64_t *dist,
+                                  int64_t *dist_mirror, double *kernel_ms)
+{
+  if (!pair_counts || n_sel <= 0 || N < 1 || N > 32767) return SR_EINVAL;
+  if (n_sel > AGREE_CHAINS_MAX) return SR_EUNSUPPORTED;
+  if (!sra_distances_host) return SR_EUNSUPPORTED;
+  float ms = 0.0f;
+  const int rc = sra_distances_host(device, N, n_sel, pair_counts, (long long *)dist, (long long *)dist_mirror, &ms);
+  if (!rc && kernel_ms) *kernel_ms = ms;
+  return post_rc(rc);
+}
+
+/* e of the pair {x, y}, read from the upper triangle */
+static int64_t agree_e(int32_t n, const int64_t *dist, const int64_t *mir, int32_t x, int32_t y, int *mirrored)
+{
+  const size_t at = x < y ? (size_t)x * n + y : (size_t)y * n + x;
+  if (mirrored) *mirrored = mir[at] < dist[at];
+  return mir[at] < dist[at] ? mir[at] : dist[at];
+}
+
+SR_API int sr_agreement_modes(int32_t n, const int64_t *dist, const int64_t *dist_mirror, int64_t scale, double threshold,
+                              int32_t *mode, uint8_t *flip, int32_t *medoid, int32_t *size, int32_t *n_modes)
+{
+  if (n <= 0 || !dist || !dist_mirror || !mode || scale < 0 || !(threshold >= 0.0 && threshold <= 1.0))
+    return SR_EINVAL;   /* NaN included */
+  int32_t *queue = (int32_t *)malloc(sizeof(int32_t) * n), *seen = (int32_t *)malloc(sizeof(int32_t) * n);
+  uint8_t *fl = (uint8_t *)malloc(n);
+  if (!queue || !seen || !fl) {
+    free(queue); free(seen); free(fl);
+    return SR_ENOMEM;
+  }
+  const double lim = threshold * (double)scale;
+  for (int32_t k = 0; k < n; k++) seen[k] = -1;   /* the mode of a chain once it is reached */
+  int32_t g = 0;
+  for (int32_t root = 0; root < n; root++) {
+    if (seen[root] >= 0) continue;
+    int32_t head = 0, tail = 0;
+    seen[root] = g;
+    fl[root] = 0;
+    queue[tail++] = root;
+    while (head < tail) {   /* breadth first: first in, first out; neighbours in ascending index */
+      const int32_t k = queue[head++];
+      for (int32_t l = 0; l < n; l++) {
+        int mirrored;
+        if (seen[l] >= 0 || !((double)agree_e(n, dist, dist_mirror, k, l, &mirrored) <= lim)) continue;
+        seen[l] = g;
+        fl[l] = (uint8_t)(fl[k] ^ mirrored);
+        queue[tail++] = l;
+      }
+    }
+    /* the medoid: the smallest (sum of e to the other members, index); a sum of up to n values below 2^60 */
+    int32_t best = root;
+    __int128 best_sum = 0;
+    for (int32_t x = 0; x < n; x++) {
+      if (seen[x] != g) continue;
+      __int128 sum = 0;
+      for (int32_t q = 0; q < tail; q++)
+        if (queue[q] != x) sum += agree_e(n, dist, dist_mirror, x, queue[q], NULL);
+      if (x == root || sum < best_sum) { best = x; best_sum = sum; }
+    }
+    if (medoid) medoid[g] = best;
+    if (size) size[g] = tail;
+    g++;
+  }
+  for (int32_t k = 0; k < n; k++) {
+    mode[k] = seen[k];
+    if (flip) flip[k] = fl[k];
+  }
+  if (n_modes) *n_modes = g;
+  free(queue); free(seen); free(fl);
+  return SR_OK;
+}
+
 /* ---- WAIC and the pointwise model fit (definitions: include/seriation.h) ---- */
 /* sr_waic.hip's entry points, weak for the same reason as the moment kernels' */
 extern __typeof__(srw_waic_dev) srw_waic_dev __attribute__((weak));

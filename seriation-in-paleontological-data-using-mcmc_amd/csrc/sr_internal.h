@@ -163,6 +163,17 @@ int srw_waic_dev(int device, void *stream, const int16_t *d_rec, const long long
 int srw_waic_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *X,
                   const double *const *cd, int cdw, int manycd, double *lppd, double *ll_mean, double *pwaic,
                   float *ms);
+/* chain agreement (sr_agree.hip): pair_counts [n_sel][N][N], dist and dist_mirror [n_sel][n_sel] over n_sel chains'
+   `count` rows (only the pi part of a row is read), exact integers; host buffers, each optional.
+   sra_distances_host is the reduction alone, from pair counts in host memory (any uint32 values).  Weak in
+   sr_host.c like the relations' entry points: sr_agreement returns SR_EUNSUPPORTED in the host-only builds. */
+int sra_agreement_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
+                      long long row_stride, int N, int M, uint32_t *pair_counts, long long *dist,
+                      long long *dist_mirror, float *ms);
+int sra_agreement_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, uint32_t *pair_counts,
+                       long long *dist, long long *dist_mirror, float *ms);
+int sra_distances_host(int device, int N, int n_sel, const uint32_t *pair_counts, long long *dist,
+                       long long *dist_mirror, float *ms);
 void srk_destroy(srk_dev *d);
 
 #ifdef __cplusplus

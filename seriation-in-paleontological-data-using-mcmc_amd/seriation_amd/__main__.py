@@ -7,7 +7,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
     python -m seriation_amd DATASET [--chains 100] [--burnin 1000] [--samples 1000] [--thin 10]
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
-                                    [--marginals] [--relations] [--waic]
+                                    [--marginals] [--relations] [--waic] [--modes [--mode-threshold X]]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -27,6 +27,13 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 chain_data.csv, shared rates or, with --manycd, per-taxon rates).  Chains/waic.csv: one row
                 elpd_waic, se, p_waic, lppd, waic, n_high (cells with p_waic above 0.4), samples, cells;
                 Chains/waic_sites.csv and Chains/waic_taxa.csv: each site's and each taxon's share of elpd_waic
+  --modes       which chains sampled the same order, over all chains of the run, before and independent of --select
+                (analysis.agreement_from_records and chain_modes over their chain_data.csv).  Chains/chain_modes.csv:
+                per chain its mode, its flip against the mode's first chain, whether it is the mode's medoid, the
+                mode's size and its distance to the medoid; Chains/chain_distances.csv: per pair k < l the order
+                distance and the distance to l's mirror image, and per chain (k, k) the distance to its own mirror
+                image; prints "modes: <n> sizes: ...".  --mode-threshold X (default 0.1, a default only: see
+                analysis.chain_modes): chains are linked when their distance is at most X of the largest possible
   --no-save     sample without writing files; prints one JSON summary per chain
   --rng         mt: GSL MT19937 as the reference (default); philox: the opt-in counter-based
                 Philox4x32-10 stream for sampling (statistically equivalent, not bit-equal)
@@ -106,6 +113,32 @@ def write_waic(ds, chains, root, manycd=False, device=0):
                 fh.write("%d,%r\n" % (i, float(r[key + "_elpd"][i])))
 
 
+def write_modes(ds, chains, root, threshold, device=0):
+    """Chains/chain_modes.csv and Chains/chain_distances.csv of all the run's chains: the order distances between
+    their chain_data.csv rows and the modes linked at `threshold`.  Returns the modes' sizes."""
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    r = analysis.agreement_from_records(ds, rec, device=device)
+    d, dm = r["dist"].tolist(), r["dist_mirror"].tolist()
+    cm = analysis.chain_modes(r["dist"], r["dist_mirror"], r["scale"], threshold)
+    n = len(chains)
+    with open(os.path.join(root, "Chains", "chain_modes.csv"), "w") as fh:
+        fh.write("chain,mode,flip,is_medoid,mode_size,dist_to_medoid\n")
+        for k in range(n):
+            g = int(cm["mode"][k])
+            c = int(cm["medoid"][g])
+            lo, hi = min(k, c), max(k, c)
+            fh.write("%d,%d,%d,%d,%d,%d\n" % (chains[k], g, cm["flip"][k], k == c, cm["size"][g],
+                                              0 if k == c else min(d[lo][hi], dm[lo][hi])))
+    with open(os.path.join(root, "Chains", "chain_distances.csv"), "w") as fh:
+        fh.write("k,l,dist,dist_mirror\n")
+        for k in range(n):
+            fh.write("%d,%d,%d,%d\n" % (chains[k], chains[k], d[k][k], dm[k][k]))
+            for l in range(k + 1, n):
+                fh.write("%d,%d,%d,%d\n" % (chains[k], chains[l], d[k][l], dm[k][l]))
+    return cm["size"].tolist()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m seriation_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("dataset")
@@ -124,7 +157,13 @@ def main(argv=None):
     ap.add_argument("--marginals", action="store_true")
     ap.add_argument("--relations", action="store_true")
     ap.add_argument("--waic", action="store_true")
+    ap.add_argument("--modes", action="store_true")
+    ap.add_argument("--mode-threshold", type=float, default=0.1)
     a = ap.parse_args(argv)
+    if a.modes and a.no_save:
+        ap.error("--modes needs the chain files: not with --no-save")
+    if a.modes and not 0.0 <= a.mode_threshold <= 1.0:
+        ap.error("--mode-threshold must lie in [0, 1]")
     if a.waic and (a.select < 1 or a.no_save):
         ap.error("--waic needs --select K (and the chain files: not with --no-save)")
     if a.marginals and (a.select < 1 or a.no_save):
@@ -157,6 +196,10 @@ def main(argv=None):
         summ = launcher.run_all_chains(a.dataset, n_chains=a.chains, seeds=seeds, devices=devices,
                                        burnin_calls=a.burnin, sample_calls=a.samples, root=a.root,
                                        sweeps_per_call=a.thin, rng=a.rng, manycd=int(a.manycd))
+        if a.modes:
+            sizes = write_modes(core.Dataset.load(a.dataset), list(range(a.chains)), a.root, a.mode_threshold,
+                                devices[0] if devices else 0)
+            print("modes: %d sizes: %s" % (len(sizes), " ".join(str(v) for v in sizes)))
         if a.select:
             chosen = launcher.choose_chains(a.select, a.root)
             print("selected:", " ".join(str(k) for k in chosen))

@@ -111,6 +111,13 @@ class sr_waic_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_agree_out(ctypes.Structure):
+    _fields_ = [("pair_counts", ctypes.POINTER(ctypes.c_uint32)),
+                ("dist", ctypes.POINTER(ctypes.c_int64)), ("dist_mirror", ctypes.POINTER(ctypes.c_int64)),
+                ("scale", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                            ctypes.POINTER(sr_record))
 
@@ -127,7 +134,9 @@ PUBLIC_SYMBOLS = [
     "sr_session_checkpoint", "sr_session_restore",
     "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior",
     "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals",
-    "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce", "sr_strerror", "sr_device_count", "sr_version",
+    "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce",
+    "sr_agreement", "sr_session_agreement", "sr_agreement_distances", "sr_agreement_modes",
+    "sr_strerror", "sr_device_count", "sr_version",
 ]
 
 _LIB = None
@@ -197,6 +206,12 @@ def _lib():
         "sr_waic": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, c_i32, P(sr_waic_out)]),
         "sr_session_waic": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_waic_out)]),
         "sr_waic_reduce": (c_int, [c_i32, c_i32, P(c_double), P(c_double), P(sr_waic_out)]),
+        "sr_agreement": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_agree_out)]),
+        "sr_session_agreement": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_agree_out)]),
+        "sr_agreement_distances": (c_int, [c_i32, c_i32, P(ctypes.c_uint32), c_i32, P(ctypes.c_int64),
+                                           P(ctypes.c_int64), P(c_double)]),
+        "sr_agreement_modes": (c_int, [c_i32, P(ctypes.c_int64), P(ctypes.c_int64), ctypes.c_int64, c_double,
+                                       P(c_i32), P(ctypes.c_uint8), P(c_i32), P(c_i32), P(c_i32)]),
         "sr_strerror": (ctypes.c_char_p, [c_int]),
         "sr_device_count": (c_int, []),
         "sr_version": (ctypes.c_char_p, []),

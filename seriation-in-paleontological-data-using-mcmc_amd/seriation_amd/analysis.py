@@ -483,6 +483,96 @@ def waic_compare(a, b):
     return {"elpd_diff": float(tot), "se_diff": float(se)}
 
 
+# ---------------------------------------------------------------- chain agreement and modes
+# Which chains sampled the same order: per chain the exact counts of every site pair's order, the L1 distance between
+# every two chains' counts, plain and against the mirror image, and the single-linkage modes read off them
+# (definitions: include/seriation.h).  Counts and distances come from the GPU (csrc/sr_agree.hip); there is no CPU
+# fallback.  The clustering is the library's host code.  Pool only the chains of one mode, with that mode's flips.
+_U32P = ctypes.POINTER(ctypes.c_uint32)
+
+
+def _agree_outs(N, n_sel, pair_counts):
+    n = max(int(n_sel), 0)
+    arrs = {"dist": np.zeros((n, n), np.int64), "dist_mirror": np.zeros((n, n), np.int64)}
+    out = L.sr_agree_out()
+    out.dist = arrs["dist"].ctypes.data_as(_I64P)
+    out.dist_mirror = arrs["dist_mirror"].ctypes.data_as(_I64P)
+    if pair_counts:
+        arrs["pair_counts"] = np.zeros((n, N, N), np.uint32)
+        out.pair_counts = arrs["pair_counts"].ctypes.data_as(_U32P)
+    return out, arrs
+
+
+def _agree_result(out, arrs):
+    arrs["scale"] = int(out.scale)
+    arrs["kernel_ms"] = out.kernel_ms
+    return arrs
+
+
+def agreement_from_records(dataset, ab_pi, pair_counts=False, device=0):
+    """sr_agreement: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order; only pi is read) ->
+    {"dist", "dist_mirror": int64 [n_sel][n_sel], "scale": count * N (N - 1) / 2, "kernel_ms"}; pair_counts=True adds
+    "pair_counts" uint32 [n_sel][N][N] (entry [k][i][j]: chain k's rows with pi_i < pi_j)."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    out, arrs = _agree_outs(dataset.N, n_sel, pair_counts)
+    _check(L.lib().sr_agreement(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n_sel,
+                                count, device, ctypes.byref(out)), "sr_agreement")
+    return _agree_result(out, arrs)
+
+
+def agreement_from_session(session, chains, first=0, count=None, pair_counts=False):
+    """sr_session_agreement: the same over a session's records still in HBM, rows [first, first + count) of chains
+    (session chain indices in selection order)."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs = _agree_outs(session.ds.N, len(chains), pair_counts)
+    _check(L.lib().sr_session_agreement(session.h, ch, len(chains), first, count, ctypes.byref(out)),
+           "sr_session_agreement")
+    return _agree_result(out, arrs)
+
+
+def agreement_distances(pair_counts, device=0):
+    """sr_agreement_distances: the reduction alone.  pair_counts uint32 [n_sel][N][N] in host memory (any values; e.g.
+    matrices gathered from several GPUs) -> {"dist", "dist_mirror": int64 [n_sel][n_sel], "kernel_ms"}."""
+    pc = np.ascontiguousarray(pair_counts, dtype=np.uint32)
+    assert pc.ndim == 3 and pc.shape[1] == pc.shape[2]
+    n = pc.shape[0]
+    arrs = {"dist": np.zeros((n, n), np.int64), "dist_mirror": np.zeros((n, n), np.int64)}
+    ms = ctypes.c_double(0.0)
+    _check(L.lib().sr_agreement_distances(pc.shape[1], n, pc.ctypes.data_as(_U32P), device,
+                                          arrs["dist"].ctypes.data_as(_I64P), arrs["dist_mirror"].ctypes.data_as(_I64P),
+                                          ctypes.byref(ms)), "sr_agreement_distances")
+    arrs["kernel_ms"] = ms.value
+    return arrs
+
+
+def chain_modes(dist, dist_mirror, scale, threshold=0.1):
+    """sr_agreement_modes (host only, no GPU): single-linkage modes of the chains.  Chains k < l are linked when
+    min(dist[k][l], dist_mirror[k][l]) <= threshold * scale -> {"mode": int32 [n] (numbered by smallest member),
+    "flip": uint8 [n], "medoid", "size": int32 [n_modes], "n_modes"}.  flip can be passed straight to the flips= of
+    marginals_* / relations_* for the chains of one mode (flip[chains_of_that_mode]).
+    The default threshold 0.1 is a default only: it rests on one measurement with the CPU oracle, one dataset
+    (g10s10, seeds 1..8) and short runs (300 burn-in + 200 saved calls), where chains of one mode lay within
+    0.035-0.066 of each other, the two halves of one chain 0.016-0.040 apart, and every other pair at 0.20-0.73.
+    Look at dist / scale of your own run before trusting it."""
+    d = np.ascontiguousarray(dist, dtype=np.int64)
+    m = np.ascontiguousarray(dist_mirror, dtype=np.int64)
+    assert d.ndim == 2 and d.shape[0] == d.shape[1] and m.shape == d.shape
+    n = d.shape[0]
+    mode, flip = np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    medoid, size = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    n_modes = ctypes.c_int32(0)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    _check(L.lib().sr_agreement_modes(n, d.ctypes.data_as(_I64P), m.ctypes.data_as(_I64P), int(scale), float(threshold),
+                                      mode.ctypes.data_as(i32p), flip.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                      medoid.ctypes.data_as(i32p), size.ctypes.data_as(i32p), ctypes.byref(n_modes)),
+           "sr_agreement_modes")
+    g = n_modes.value
+    return {"mode": mode, "flip": flip, "medoid": medoid[:g].copy(), "size": size[:g].copy(), "n_modes": g}
+
+
 def read_chain_cd(root, chains, taxa, manycd=False):
     """chain_data.csv of each chain -> the rates on the log scale, c = math.log(float(token)) of fields 3 and 4:
     float64 [n][lines][3] (the first c and d token and field 5, the line's loglik) or, manycd, [n][lines][2M] (all M
