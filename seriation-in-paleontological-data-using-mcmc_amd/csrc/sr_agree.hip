@@ -34,13 +34,17 @@
  * from the first add on: per lane, per wave (shuffles), per block (LDS), and the one 64-bit integer atomic add per
  * (k, l) and block.  Fewer than 2^29 pairs i < j exist (N <= 32767), so no sum, partial or final, over any set of
  * pairs exceeds 2^29 (2^32 - 1) < 2^61.
+ *
+ * The rows are addressed through a record view (sr_records.h: chain k's rows start at rec + chain_off[k], row_stride
+ * apart); sra_agreement is the unit's entry point over records, sra_distances_host the reduction alone.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include "sr_internal.h"
+#include "sr_records.h"
+#include "sr_analysis.h"
 
 #define SRA_TILE 64                      /* pair kernel: the tile is SRA_TILE x SRA_TILE site pairs */
 #define SRA_TE (SRA_TILE * SRA_TILE)     /* scratch entries of a tile, per order */
@@ -184,9 +188,6 @@ __global__ __launch_bounds__(SRA_THREADS) void sr_agree_dist_kernel(const unsign
   }
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-  fprintf(stderr, "seriation: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); rc = -5; goto done; } } while (0)
-
 static long long sra_scratch_limit(void)
 {
   const char *e = getenv("SR_AGREE_SCRATCH");
@@ -221,19 +222,19 @@ static hipError_t sra_dist_launch(hipStream_t st, int resident, const unsigned *
   return hipGetLastError();
 }
 
-/* The agreement of n_sel chains' device-resident records.  pair_counts [n_sel][N][N], dist and dist_mirror
+/* The agreement of the n_sel chains of a record view.  pair_counts [n_sel][N][N], dist and dist_mirror
    [n_sel][n_sel] are host buffers, each optional. */
-extern "C" int sra_agreement_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel,
-                                 int count, long long row_stride, int N, int M, uint32_t *pair_counts, long long *dist,
-                                 long long *dist_mirror, float *ms)
+extern "C" int sra_agreement(const sr_recview *v, int N, int M, uint32_t *pair_counts, long long *dist,
+                             long long *dist_mirror, float *ms)
 {
   int rc = 0;
-  long long *d_off = nullptr;
   unsigned *d_S = nullptr, *d_pc = nullptr;
   unsigned long long *d_dm = nullptr;   /* dist, then dist_mirror */
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!d_rec || !chain_off || n_sel <= 0 || n_sel > 4096 || count < 1 || N < 1 || N > 32767 || M < 1) return -1;
+  if (!v) return -1;
+  const int n_sel = v->n_sel, count = v->count;
+  hipStream_t st = (hipStream_t)v->stream;
+  if (!v->rec || !v->chain_off || n_sel <= 0 || n_sel > 4096 || count < 1 || N < 1 || N > 32767 || M < 1) return -1;
   if (ms) *ms = 0.0f;
   const bool want_d = dist || dist_mirror;
   const int nt = (N + SRA_TILE - 1) / SRA_TILE;
@@ -247,15 +248,13 @@ extern "C" int sra_agreement_dev(int device, void *stream, const int16_t *d_rec,
   }
   {
     int ncu = 0, per_cu = 0, per_cu_d = 0;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, v->device));
     if (ncu < 1) ncu = 1;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sr_agree_pair_kernel, SRA_THREADS, 0));
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, sr_agree_dist_kernel, SRA_THREADS, 0));
     if (per_cu < 1) per_cu = 1;
     if (per_cu_d < 1) per_cu_d = 1;
-    HIPCHK(hipMalloc(&d_off, sizeof(long long) * n_sel));
-    HIPCHK(hipMemcpy(d_off, chain_off, sizeof(long long) * n_sel, hipMemcpyHostToDevice));
     if (pair_counts) HIPCHK(hipMalloc(&d_pc, pc_bytes));
     if (want_d) {
       HIPCHK(hipMalloc(&d_S, (size_t)n_sel * 2 * max_tiles * SRA_TE * sizeof(unsigned)));
@@ -264,7 +263,7 @@ extern "C" int sra_agreement_dev(int device, void *stream, const int16_t *d_rec,
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
     AgreeArgs A;
-    A.rec = d_rec; A.chain_off = d_off; A.row_stride = row_stride;
+    A.rec = v->rec; A.chain_off = v->chain_off; A.row_stride = v->row_stride;
     A.count = count; A.N = N; A.pi_off = 2 * M; A.nt = nt;
     A.scratch = d_S; A.pc = d_pc;
     HIPCHK(hipEventRecord(e0, st));
@@ -272,13 +271,8 @@ extern "C" int sra_agreement_dev(int device, void *stream, const int16_t *d_rec,
     if (d_dm) HIPCHK(hipMemsetAsync(d_dm, 0, 2 * nn * sizeof(unsigned long long), st));
     for (int I0 = 0, I1; I0 < nt; I0 = I1) {
       const long long tiles = sra_band(nt, I0, n_sel, limit, &I1);
-      /* the chain's rows cut into as many pieces as keep the resident blocks busy in one round */
-      long long nz = (long long)ncu * per_cu / (tiles * n_sel), nzmax = count / SRA_MIN_ROWS;
-      if (nz > nzmax) nz = nzmax;
-      if (nz > 65535) nz = 65535;
-      if (nz < 1) nz = 1;
-      A.rows_per_piece = (int)((count + nz - 1) / nz);
-      nz = (count + A.rows_per_piece - 1) / A.rows_per_piece;
+      long long nz;   /* pieces of a chain's rows */
+      A.rows_per_piece = (int)sr_pieces((long long)ncu * per_cu, tiles * n_sel, count, SRA_MIN_ROWS, SR_GRID_CAP, &nz);
       A.I0 = I0;
       A.E = tiles * SRA_TE;
       if (d_S) HIPCHK(hipMemsetAsync(d_S, 0, (size_t)n_sel * 2 * A.E * sizeof(unsigned), st));
@@ -296,41 +290,15 @@ extern "C" int sra_agreement_dev(int device, void *stream, const int16_t *d_rec,
 done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (d_off) (void)hipFree(d_off);
   if (d_S) (void)hipFree(d_S);
   if (d_pc) (void)hipFree(d_pc);
   if (d_dm) (void)hipFree(d_dm);
   return rc;
 }
 
-/* Records from host memory: ab_pi [n_sel][count][2M+N] int16 (selection order). */
-extern "C" int sra_agreement_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M,
-                                  uint32_t *pair_counts, long long *dist, long long *dist_mirror, float *ms)
-{
-  int rc = 0;
-  int16_t *d_rec = nullptr;
-  long long *off = nullptr;
-  if (!ab_pi || n_sel <= 0 || count < 1 || N < 1 || M < 1) return -1;
-  const long long W = 2LL * M + N;
-  const size_t bytes = (size_t)n_sel * count * W * sizeof(int16_t);
-  off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return -4;
-  for (int k = 0; k < n_sel; ++k) off[k] = (long long)k * count * W;
-  {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_rec, bytes));
-    HIPCHK(hipMemcpy(d_rec, ab_pi, bytes, hipMemcpyHostToDevice));
-    rc = sra_agreement_dev(device, nullptr, d_rec, off, n_sel, count, W, N, M, pair_counts, dist, dist_mirror, ms);
-  }
-done:
-  if (d_rec) (void)hipFree(d_rec);
-  free(off);
-  return rc;
-}
-
 /* The distances alone, from pair counts in host memory: pair_counts [n_sel][N][N], any uint32 values.  The host
    packs a band of the matrices into the scratch layout (both orders of every pair i < j, the other entries 0); the
-   bands and the distance kernel are those of sra_agreement_dev. */
+   bands and the distance kernel are those of sra_agreement. */
 extern "C" int sra_distances_host(int device, int N, int n_sel, const uint32_t *pair_counts, long long *dist,
                                   long long *dist_mirror, float *ms)
 {

@@ -20,11 +20,16 @@
  * accumulate in 64 bits.  All LDS is dynamic: the tile with its zero rows, then SRD_TAIL bytes for the block's
  * largest |x|; (h + 32) * 128 + 16 <= 163840 holds up to h = 1247.  Longer sequences (h >= 1248) read their
  * rows from global memory (L2-resident: a tile is h x 128 bytes) through the same loops.
+ *
+ * The rows are addressed through a record view (sr_records.h: chain k's rows start at rec + chain_off[k],
+ * row_stride apart); srd_moments is the unit's one entry point, and a batch of a session's chains is a slice of
+ * the session's view.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include "sr_internal.h"
+#include "sr_records.h"
+#include "sr_analysis.h"
 
 #define TCOL 64   /* columns per block (lanes) */
 #define KL 16     /* lags per pass */
@@ -141,30 +146,26 @@ __global__ __launch_bounds__(256) void sr_diag_kernel(DiagArgs A)
   }
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-  fprintf(stderr, "seriation: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); rc = -5; goto done; } } while (0)
-
-/* The moments of n_sel chains' device-resident records (S = 2 n_sel sequences, h = count / 2, lags 0..L);
+/* The moments of the n_sel chains of a record view (S = 2 n_sel sequences, h = count / 2, lags 0..L);
    P, F, B [S][L+1][W] and S1 [S][W] are host buffers. */
-extern "C" int srd_moments_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel,
-                               int count, long long row_stride, int W, int L, long long *P, long long *F, long long *B,
-                               long long *S1, float *ms)
+extern "C" int srd_moments(const sr_recview *v, int W, int L, long long *P, long long *F, long long *B, long long *S1,
+                           float *ms)
 {
   int rc = 0;
-  long long *d_off = nullptr, *d_out = nullptr;
+  long long *d_out = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = (hipStream_t)stream;
+  if (!v) return -1;
+  const int n_sel = v->n_sel, count = v->count;
+  hipStream_t st = (hipStream_t)v->stream;
   const int h = count / 2;
-  if (!d_rec || !chain_off || !P || !F || !B || !S1 || n_sel <= 0 || count < 4 || W < 1 || L < 1 || L >= h) return -1;
+  if (!v->rec || !v->chain_off || !P || !F || !B || !S1 || n_sel <= 0 || count < 4 || W < 1 || L < 1 || L >= h) return -1;
   if (2LL * n_sel > 65535) return -1;   /* one grid row per sequence */
   const size_t S = 2 * (size_t)n_sel, lw = (size_t)(L + 1) * W, nP = S * lw, nS = S * (size_t)W;
   {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_off, sizeof(long long) * n_sel));
-    HIPCHK(hipMemcpy(d_off, chain_off, sizeof(long long) * n_sel, hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(v->device));
     HIPCHK(hipMalloc(&d_out, sizeof(long long) * (3 * nP + nS)));
     DiagArgs A;
-    A.rec = d_rec; A.chain_off = d_off; A.row_stride = row_stride;
+    A.rec = v->rec; A.chain_off = v->chain_off; A.row_stride = v->row_stride;
     A.count = count; A.h = h; A.L = L; A.W = W;
     A.P = d_out; A.F = d_out + nP; A.B = d_out + 2 * nP; A.S1 = d_out + 3 * nP;
     const size_t tile = (size_t)(h + PADR) * TCOL * sizeof(int16_t);
@@ -190,31 +191,6 @@ extern "C" int srd_moments_dev(int device, void *stream, const int16_t *d_rec, c
 done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (d_off) (void)hipFree(d_off);
   if (d_out) (void)hipFree(d_out);
-  return rc;
-}
-
-/* Records from host memory: ab_pi [n_sel][count][W] int16 (selection order). */
-extern "C" int srd_moments_host(int device, const int16_t *ab_pi, int n_sel, int count, int W, int L, long long *P,
-                                long long *F, long long *B, long long *S1, float *ms)
-{
-  int rc = 0;
-  int16_t *d_rec = nullptr;
-  long long *off = nullptr;
-  if (!ab_pi || n_sel <= 0 || count < 4 || W < 1) return -1;
-  const size_t bytes = (size_t)n_sel * count * W * sizeof(int16_t);
-  off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return -4;
-  for (int k = 0; k < n_sel; ++k) off[k] = (long long)k * count * W;
-  {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_rec, bytes));
-    HIPCHK(hipMemcpy(d_rec, ab_pi, bytes, hipMemcpyHostToDevice));
-    rc = srd_moments_dev(device, nullptr, d_rec, off, n_sel, count, W, W, L, P, F, B, S1, ms);
-  }
-done:
-  if (d_rec) (void)hipFree(d_rec);
-  free(off);
   return rc;
 }

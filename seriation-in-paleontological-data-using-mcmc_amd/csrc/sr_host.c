@@ -26,6 +26,7 @@
 #include <unistd.h>
 #include "seriation.h"
 #include "sr_internal.h"
+#include "sr_records.h"
 #include "sr_math.h"
 #include "sr_rng.h"
 
@@ -1048,30 +1049,37 @@ static double *post_slot(sr_posterior_out *o, int k)
   }
 }
 
-static int post_rc(int rc) { return rc == 0 ? SR_OK : (rc == -1 ? SR_EINVAL : (rc == -4 ? SR_ENOMEM : SR_EDEVICE)); }
+/* ---- the record view of the analyses below (sr_records.h) ---- */
+/* The view's functions (sr_records.hip) and the analyses' entry points (sr_post, sr_diag, sr_marg, sr_rel, sr_agree,
+   sr_waic .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
+   every analysis reports SR_EUNSUPPORTED, after its argument checks and before anything is uploaded. */
+#define SR_WEAK(f) extern __typeof__(f) f __attribute__((weak))
+SR_WEAK(sr_recview_host);
+SR_WEAK(sr_recview_device);
+SR_WEAK(sr_recview_release);
+SR_WEAK(srp_posterior);
+SR_WEAK(srd_moments);
+SR_WEAK(srm_marginals);
+SR_WEAK(srr_relations);
+SR_WEAK(sra_agreement);
+SR_WEAK(sra_distances_host);
+SR_WEAK(srw_waic);
 
-SR_API int sr_posterior(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count,
-                        int32_t chains_selected, int32_t device, sr_posterior_out *out)
-{
-  if (!ds || !ab_pi || !out || n_sel <= 0 || count < 0 || chains_selected == 0) return SR_EINVAL;
-  for (int k = 0; k < 6; k++) {
-    double *dst = post_slot(out, k);
-    if (!dst) continue;
-    float ms = 0.0f;
-    int rc = srp_posterior_host(device, post_kinds[k], ab_pi, n_sel, count, ds->N, ds->M, ds->X, chains_selected, dst, &ms);
-    if (rc) return post_rc(rc);
-    out->kernel_ms += ms;
-  }
-  return SR_OK;
-}
+/* the device layer's return code (0, -1, -4, anything else) as an SR_* code */
+static int sr_code_of(int rc) { return rc == 0 ? SR_OK : (rc == -1 ? SR_EINVAL : (rc == -4 ? SR_ENOMEM : SR_EDEVICE)); }
 
-SR_API int sr_session_posterior(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
-                                int32_t chains_selected, sr_posterior_out *out)
+/* The view of a session selection, rows [first, first + count) of chains[0..n_sel) (n_sel > 0): the records stay
+   where they are in HBM, the offsets are uploaded.  SR_EINVAL unless the rows are saved ones (count > nrec - first
+   cannot overflow where first + count > nrec would) and the chains the session's.  `refuse` is the caller's own
+   reason not to go on (SR_OK: none; else SR_EUNSUPPORTED: no kernels in this build, an output too large): only the
+   selection's SR_EINVAL beats it, and it is returned before the device is touched. */
+static int session_view(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count, int refuse,
+                        sr_recview *v)
 {
-  if (!s || !chains || !out || n_sel <= 0 || first < 0 || count < 0 || first + count > s->nrec || chains_selected == 0)
-    return SR_EINVAL;
+  if (first < 0 || first > s->nrec || count < 0 || count > s->nrec - first) return SR_EINVAL;
   for (int k = 0; k < n_sel; k++)
     if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  if (refuse) return refuse;
   const int16_t *rec;
   int cap, dev;
   void *stream;
@@ -1080,25 +1088,49 @@ SR_API int sr_session_posterior(sr_session *s, const int32_t *chains, int32_t n_
   long long *off = (long long *)malloc(sizeof(long long) * n_sel);
   if (!off) return SR_ENOMEM;
   for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
+  const int rc = sr_code_of(sr_recview_device(v, dev, stream, rec, off, n_sel, count, W));
+  free(off);
+  return rc;
+}
+
+static int post_run(const sr_recview *v, const sr_dataset *ds, int32_t chains_selected, sr_posterior_out *out)
+{
   int rc = 0;
   for (int k = 0; k < 6 && !rc; k++) {
     double *dst = post_slot(out, k);
     if (!dst) continue;
     float ms = 0.0f;
-    rc = srp_posterior_dev(dev, stream, post_kinds[k], rec, off, n_sel, count, W, s->ds.N, s->ds.M, s->ds.X,
-                           chains_selected, dst, &ms);
-    out->kernel_ms += ms;
+    rc = srp_posterior(v, post_kinds[k], ds->N, ds->M, ds->X, chains_selected, dst, &ms);
+    if (!rc) out->kernel_ms += ms;
   }
-  free(off);
-  return post_rc(rc);
+  return sr_code_of(rc);
+}
+
+SR_API int sr_posterior(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count,
+                        int32_t chains_selected, int32_t device, sr_posterior_out *out)
+{
+  if (!ds || !ab_pi || !out || n_sel <= 0 || count < 0 || chains_selected == 0) return SR_EINVAL;
+  if (!srp_posterior) return SR_EUNSUPPORTED;
+  sr_recview v;
+  int rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = post_run(&v, ds, chains_selected, out);
+  sr_recview_release(&v);
+  return rc;
+}
+
+SR_API int sr_session_posterior(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                int32_t chains_selected, sr_posterior_out *out)
+{
+  if (!s || !chains || !out || n_sel <= 0 || chains_selected == 0) return SR_EINVAL;
+  sr_recview v;
+  int rc = session_view(s, chains, n_sel, first, count, srp_posterior ? SR_OK : SR_EUNSUPPORTED, &v);
+  if (rc) return rc;
+  rc = post_run(&v, &s->ds, chains_selected, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 /* ---- convergence diagnostics: split-R-hat and ESS (definitions: include/seriation.h) ---- */
-/* The device layer's moment kernels (sr_diag.hip); absent from the host-only builds, whose device stubs
-   predate them: weak, so those builds link and sr_diagnostics reports SR_EUNSUPPORTED. */
-extern __typeof__(srd_moments_dev) srd_moments_dev __attribute__((weak));
-extern __typeof__(srd_moments_host) srd_moments_host __attribute__((weak));
-
 /* Running sums over the sequences, fed in ascending sequence order (so any number of sequences at a time). */
 typedef struct {
   int W, Q, S, h, L, ns;        /* ns: integer sequences added so far */
@@ -1252,13 +1284,14 @@ SR_API int sr_diag_reduce(int32_t W, int32_t n_sel, int32_t count, int32_t max_l
 }
 
 /* Both public forms: the moments of the chains in batches (bounded host and device buffers: the moments of 100
-   chains x 500 lags x 1280 columns are 3 GB), each batch reduced into the running sums.  rec = NULL: records in
-   host memory (ab_pi, chain k at k * count * W); else the device buffer rec with per-chain offsets off. */
+   chains x 500 lags x 1280 columns are 3 GB), each batch reduced into the running sums.  sv: the session's view,
+   of which a batch is a slice; NULL: records in host memory (ab_pi, chain k at k * count * W), of which a batch is
+   uploaded as a view of its own, so that only one batch of records is on the device at a time. */
 #define DIAG_BATCH_BYTES (256u << 20)
-static int diag_run(int W, int n_sel, int count, int L, const int16_t *ab_pi, int device, void *stream,
-                    const int16_t *rec, const long long *off, long long row_stride, const double *cdl, sr_diag_out *out)
+static int diag_run(int W, int n_sel, int count, int L, const sr_recview *sv, const int16_t *ab_pi, int device,
+                    const double *cdl, sr_diag_out *out)
 {
-  if (!srd_moments_dev || !srd_moments_host) return SR_EUNSUPPORTED;
+  if (!srd_moments) return SR_EUNSUPPORTED;
   const size_t lw = (size_t)(L + 1) * W, per_chain = 2 * lw * 3 * sizeof(int64_t);
   int nb = (int)(DIAG_BATCH_BYTES / per_chain);
   if (nb < 1) nb = 1;
@@ -1279,11 +1312,13 @@ static int diag_run(int W, int n_sel, int count, int L, const int16_t *ab_pi, in
     int64_t *bP = out->P ? out->P + 2 * c0 * lw : tP, *bF = out->F ? out->F + 2 * c0 * lw : tF;
     int64_t *bB = out->B ? out->B + 2 * c0 * lw : tB, *bS = out->S1 ? out->S1 + 2 * (size_t)c0 * W : tS;
     float ms = 0.0f;
-    int drc = rec ? srd_moments_dev(device, stream, rec, off + c0, n, count, row_stride, W, L, (long long *)bP,
-                                    (long long *)bF, (long long *)bB, (long long *)bS, &ms)
-                  : srd_moments_host(device, ab_pi + (size_t)c0 * count * W, n, count, W, L, (long long *)bP,
-                                     (long long *)bF, (long long *)bB, (long long *)bS, &ms);
-    if (drc) { rc = post_rc(drc); break; }
+    sr_recview bv;
+    int drc = 0;
+    if (sv) bv = sr_recview_chains(sv, c0, n);
+    else drc = sr_recview_host(&bv, device, ab_pi + (size_t)c0 * count * W, n, count, W);
+    if (!drc) drc = srd_moments(&bv, W, L, (long long *)bP, (long long *)bF, (long long *)bB, (long long *)bS, &ms);
+    if (!sv) sr_recview_release(&bv);
+    if (drc) { rc = sr_code_of(drc); break; }
     out->kernel_ms += ms;
     diag_add_int(&a, 2 * n, bP, bF, bB, bS);
   }
@@ -1307,42 +1342,29 @@ SR_API int sr_diagnostics(const sr_dataset *ds, const int16_t *ab_pi, const doub
   if (!ds || !ab_pi || !out || n_sel <= 0 || n_sel > INT32_MAX / 2 || ds->N < 1 || ds->M < 1) return SR_EINVAL;
   const int L = diag_lags(count, out->max_lag);
   if (L < 0) return SR_EINVAL;
-  return diag_run(2 * ds->M + ds->N, n_sel, count, L, ab_pi, device, NULL, NULL, NULL, 0, cdl, out);
+  return diag_run(2 * ds->M + ds->N, n_sel, count, L, NULL, ab_pi, device, cdl, out);
 }
 
 SR_API int sr_session_diagnostics(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
                                   sr_diag_out *out)
 {
-  if (!s || !chains || !out || n_sel <= 0 || n_sel > INT32_MAX / 2 || first < 0 || count < 0 || first + count > s->nrec)
-    return SR_EINVAL;
-  for (int k = 0; k < n_sel; k++)
-    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  if (!s || !chains || !out || n_sel <= 0 || n_sel > INT32_MAX / 2) return SR_EINVAL;
   const int L = diag_lags(count, out->max_lag);
   if (L < 0) return SR_EINVAL;
-  if (!srd_moments_dev) return SR_EUNSUPPORTED;
-  const int16_t *rec;
-  int cap, dev;
-  void *stream;
-  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
-  const int W = 2 * s->ds.M + s->ds.N;
-  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
+  sr_recview v;
+  int rc = session_view(s, chains, n_sel, first, count, srd_moments ? SR_OK : SR_EUNSUPPORTED, &v);
+  if (rc) return rc;
   double *cdl = (double *)malloc(sizeof(double) * 3 * (size_t)n_sel * count);   /* the scalar columns: to the host */
-  int rc = (off && cdl) ? SR_OK : SR_ENOMEM;
-  for (int k = 0; k < n_sel && !rc; k++) {
-    off[k] = ((long long)chains[k] * cap + first) * W;
+  if (!cdl) rc = SR_ENOMEM;
+  for (int k = 0; k < n_sel && !rc; k++)
     if (srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, cdl + (size_t)k * count * 3)) rc = SR_EDEVICE;
-  }
-  if (!rc) rc = diag_run(W, n_sel, count, L, NULL, dev, stream, rec, off, W, cdl, out);
-  free(off);
+  if (!rc) rc = diag_run(2 * s->ds.M + s->ds.N, n_sel, count, L, &v, NULL, 0, cdl, out);
+  sr_recview_release(&v);
   free(cdl);
   return rc;
 }
 
 /* ---- posterior marginals: histograms, quantiles, modes, means (definitions: include/seriation.h) ---- */
-/* sr_marg.hip's entry points, weak for the same reason as the moment kernels' */
-extern __typeof__(srm_marginals_dev) srm_marginals_dev __attribute__((weak));
-extern __typeof__(srm_marginals_host) srm_marginals_host __attribute__((weak));
-
 /* the argument checks both forms share, made before any device call */
 static int marg_check(const sr_marg_out *out, int32_t n_sel, int32_t count)
 {
@@ -1353,18 +1375,27 @@ static int marg_check(const sr_marg_out *out, int32_t n_sel, int32_t count)
   return SR_OK;
 }
 
+static int marg_run(const sr_recview *v, const sr_dataset *ds, sr_marg_out *out)
+{
+  float ms = 0.0f;
+  const int rc = srm_marginals(v, ds->N, ds->M, out->flip, out->probs, out->n_probs, out->hist, out->outside,
+                               (long long *)out->pi_sum, out->quant, out->mode, out->mean, &ms);
+  out->kernel_ms = ms;
+  return sr_code_of(rc);
+}
+
 SR_API int sr_marginals(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
                         sr_marg_out *out)
 {
   if (!ds || !ab_pi || ds->N < 1 || ds->N > 32767 || ds->M < 1) return SR_EINVAL;
   int rc = marg_check(out, n_sel, count);
   if (rc) return rc;
-  if (!srm_marginals_host) return SR_EUNSUPPORTED;
-  float ms = 0.0f;
-  rc = srm_marginals_host(device, ab_pi, n_sel, count, ds->N, ds->M, out->flip, out->probs, out->n_probs, out->hist,
-                          out->outside, (long long *)out->pi_sum, out->quant, out->mode, out->mean, &ms);
-  out->kernel_ms = ms;
-  return post_rc(rc);
+  if (!srm_marginals) return SR_EUNSUPPORTED;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = marg_run(&v, ds, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 SR_API int sr_session_marginals(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
@@ -1373,31 +1404,16 @@ SR_API int sr_session_marginals(sr_session *s, const int32_t *chains, int32_t n_
   if (!s || !chains) return SR_EINVAL;
   int rc = marg_check(out, n_sel, count);
   if (rc) return rc;
-  if (first < 0 || first > s->nrec || count > s->nrec - first || s->ds.N > 32767) return SR_EINVAL;
-  for (int k = 0; k < n_sel; k++)
-    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
-  if (!srm_marginals_dev) return SR_EUNSUPPORTED;
-  const int16_t *rec;
-  int cap, dev;
-  void *stream;
-  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
-  const long long W = 2LL * s->ds.M + s->ds.N;
-  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return SR_ENOMEM;
-  for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
-  float ms = 0.0f;
-  rc = srm_marginals_dev(dev, stream, rec, off, n_sel, count, W, s->ds.N, s->ds.M, out->flip, out->probs, out->n_probs,
-                         out->hist, out->outside, (long long *)out->pi_sum, out->quant, out->mode, out->mean, &ms);
-  out->kernel_ms = ms;
-  free(off);
-  return post_rc(rc);
+  if (s->ds.N > 32767) return SR_EINVAL;
+  sr_recview v;
+  rc = session_view(s, chains, n_sel, first, count, srm_marginals ? SR_OK : SR_EUNSUPPORTED, &v);
+  if (rc) return rc;
+  rc = marg_run(&v, &s->ds, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 /* ---- taxon-pair relations, durations, richness: exact counts (definitions: include/seriation.h) ---- */
-/* sr_rel.hip's entry points, weak for the same reason as the moment kernels' */
-extern __typeof__(srr_relations_dev) srr_relations_dev __attribute__((weak));
-extern __typeof__(srr_relations_host) srr_relations_host __attribute__((weak));
-
 #define REL_OUT_MAX ((int64_t)1 << 28)   /* uint32 entries of one output: 1 GiB */
 
 /* the argument checks both forms share, made before any device call */
@@ -1412,19 +1428,27 @@ static int rel_check(const sr_rel_out *out, int32_t n_sel, int32_t count, int32_
   return SR_OK;
 }
 
+static int rel_run(const sr_recview *v, const sr_dataset *ds, sr_rel_out *out)
+{
+  uint32_t *const pair[4] = {out->orig_before, out->ext_before, out->precedes, out->overlap};
+  float ms = 0.0f;
+  const int rc = srr_relations(v, ds->N, ds->M, out->flip, pair, out->dur_hist, out->dur_outside, out->rich_hist, &ms);
+  out->kernel_ms = ms;
+  return sr_code_of(rc);
+}
+
 SR_API int sr_relations(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
                         sr_rel_out *out)
 {
   if (!ds || !ab_pi) return SR_EINVAL;
   int rc = rel_check(out, n_sel, count, ds->N, ds->M);
   if (rc) return rc;
-  if (!srr_relations_host) return SR_EUNSUPPORTED;
-  uint32_t *const pair[4] = {out->orig_before, out->ext_before, out->precedes, out->overlap};
-  float ms = 0.0f;
-  rc = srr_relations_host(device, ab_pi, n_sel, count, ds->N, ds->M, out->flip, pair, out->dur_hist, out->dur_outside,
-                          out->rich_hist, &ms);
-  out->kernel_ms = ms;
-  return post_rc(rc);
+  if (!srr_relations) return SR_EUNSUPPORTED;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = rel_run(&v, ds, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 SR_API int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
@@ -1433,34 +1457,15 @@ SR_API int sr_session_relations(sr_session *s, const int32_t *chains, int32_t n_
   if (!s || !chains) return SR_EINVAL;
   int rc = rel_check(out, n_sel, count, s->ds.N, s->ds.M);
   if (rc == SR_EINVAL) return rc;
-  if (first < 0 || first > s->nrec || count > s->nrec - first) return SR_EINVAL;
-  for (int k = 0; k < n_sel; k++)
-    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  sr_recview v;   /* an invalid selection wins over an output too large */
+  rc = session_view(s, chains, n_sel, first, count, rc ? rc : (srr_relations ? SR_OK : SR_EUNSUPPORTED), &v);
   if (rc) return rc;
-  if (!srr_relations_dev) return SR_EUNSUPPORTED;
-  const int16_t *rec;
-  int cap, dev;
-  void *stream;
-  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
-  const long long W = 2LL * s->ds.M + s->ds.N;
-  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return SR_ENOMEM;
-  for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
-  uint32_t *const pair[4] = {out->orig_before, out->ext_before, out->precedes, out->overlap};
-  float ms = 0.0f;
-  rc = srr_relations_dev(dev, stream, rec, off, n_sel, count, W, s->ds.N, s->ds.M, out->flip, pair, out->dur_hist,
-                         out->dur_outside, out->rich_hist, &ms);
-  out->kernel_ms = ms;
-  free(off);
-  return post_rc(rc);
+  rc = rel_run(&v, &s->ds, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 /* ---- chain agreement: pairwise order distances and mode clustering (definitions: include/seriation.h) ---- */
-/* sr_agree.hip's entry points, weak for the same reason as the moment kernels' */
-extern __typeof__(sra_agreement_dev) sra_agreement_dev __attribute__((weak));
-extern __typeof__(sra_agreement_host) sra_agreement_host __attribute__((weak));
-extern __typeof__(sra_distances_host) sra_distances_host __attribute__((weak));
-
 #define AGREE_CHAINS_MAX 4096
 
 /* the argument checks both forms share, made before any device call */
@@ -1473,10 +1478,16 @@ static int agree_check(const sr_agree_out *out, int32_t n_sel, int32_t count, in
   return SR_OK;
 }
 
-static void agree_done(sr_agree_out *out, int32_t count, int32_t N, float ms)
+static int agree_run(const sr_recview *v, const sr_dataset *ds, sr_agree_out *out)
 {
-  out->scale = (int64_t)count * ((int64_t)N * (N - 1) / 2);
-  out->kernel_ms = ms;
+  float ms = 0.0f;
+  const int rc = sra_agreement(v, ds->N, ds->M, out->pair_counts, (long long *)out->dist, (long long *)out->dist_mirror,
+                               &ms);
+  if (!rc) {
+    out->scale = (int64_t)v->count * ((int64_t)ds->N * (ds->N - 1) / 2);
+    out->kernel_ms = ms;
+  }
+  return sr_code_of(rc);
 }
 
 SR_API int sr_agreement(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
@@ -1485,12 +1496,12 @@ SR_API int sr_agreement(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_se
   if (!ds || !ab_pi) return SR_EINVAL;
   int rc = agree_check(out, n_sel, count, ds->N, ds->M);
   if (rc) return rc;
-  if (!sra_agreement_host) return SR_EUNSUPPORTED;
-  float ms = 0.0f;
-  rc = sra_agreement_host(device, ab_pi, n_sel, count, ds->N, ds->M, out->pair_counts, (long long *)out->dist,
-                          (long long *)out->dist_mirror, &ms);
-  if (!rc) agree_done(out, count, ds->N, ms);
-  return post_rc(rc);
+  if (!sra_agreement) return SR_EUNSUPPORTED;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = agree_run(&v, ds, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 SR_API int sr_session_agreement(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
@@ -1499,25 +1510,12 @@ SR_API int sr_session_agreement(sr_session *s, const int32_t *chains, int32_t n_
   if (!s || !chains) return SR_EINVAL;
   int rc = agree_check(out, n_sel, count, s->ds.N, s->ds.M);
   if (rc == SR_EINVAL) return rc;
-  if (first < 0 || first > s->nrec || count > s->nrec - first) return SR_EINVAL;
-  for (int k = 0; k < n_sel; k++)
-    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
+  sr_recview v;   /* an invalid selection wins over too many chains or an output too large */
+  rc = session_view(s, chains, n_sel, first, count, rc ? rc : (sra_agreement ? SR_OK : SR_EUNSUPPORTED), &v);
   if (rc) return rc;
-  if (!sra_agreement_dev) return SR_EUNSUPPORTED;
-  const int16_t *rec;
-  int cap, dev;
-  void *stream;
-  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
-  const long long W = 2LL * s->ds.M + s->ds.N;
-  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return SR_ENOMEM;
-  for (int k = 0; k < n_sel; k++) off[k] = ((long long)chains[k] * cap + first) * W;
-  float ms = 0.0f;
-  rc = sra_agreement_dev(dev, stream, rec, off, n_sel, count, W, s->ds.N, s->ds.M, out->pair_counts,
-                         (long long *)out->dist, (long long *)out->dist_mirror, &ms);
-  if (!rc) agree_done(out, count, s->ds.N, ms);
-  free(off);
-  return post_rc(rc);
+  rc = agree_run(&v, &s->ds, out);
+  sr_recview_release(&v);
+  return rc;
 }
 
 SR_API int sr_agreement_distances(int32_t N, int32_t n_sel, const uint32_t *pair_counts, int32_t device, int64_t *dist,
@@ -1529,7 +1527,7 @@ SR_API int sr_agreement_distances(int32_t N, int32_t n_sel, const uint32_t *pair
   float ms = 0.0f;
   const int rc = sra_distances_host(device, N, n_sel, pair_counts, (long long *)dist, (long long *)dist_mirror, &ms);
   if (!rc && kernel_ms) *kernel_ms = ms;
-  return post_rc(rc);
+  return sr_code_of(rc);
 }
 
 /* e of the pair {x, y}, read from the upper triangle */
@@ -1594,10 +1592,6 @@ SR_API int sr_agreement_modes(int32_t n, const int64_t *dist, const int64_t *dis
 }
 
 /* ---- WAIC and the pointwise model fit (definitions: include/seriation.h) ---- */
-/* sr_waic.hip's entry points, weak for the same reason as the moment kernels' */
-extern __typeof__(srw_waic_dev) srw_waic_dev __attribute__((weak));
-extern __typeof__(srw_waic_host) srw_waic_host __attribute__((weak));
-
 #define WAIC_CELLS_MAX ((int64_t)1 << 27)
 
 SR_API int sr_waic_reduce(int32_t N, int32_t M, const double *lppd, const double *pwaic, sr_waic_out *out)
@@ -1660,20 +1654,16 @@ static int waic_cd_ok(const double *cd, int32_t count, int cdw, int Mt)
 }
 
 /* the pointwise arrays the caller did not ask for are temporaries here: the reduction needs lppd and pwaic */
-static int waic_run(int N, int M, sr_waic_out *out, int dev_form, int device, void *stream, const int16_t *rec,
-                    const long long *off, long long W, const int16_t *ab_pi, int32_t n_sel, int32_t count,
-                    const uint8_t *X, const double *const *cd, int cdw, int manycd)
+static int waic_run(const sr_recview *v, const sr_dataset *ds, sr_waic_out *out, const double *const *cd, int cdw,
+                    int manycd)
 {
+  const int N = ds->N, M = ds->M;
   const size_t nm = (size_t)N * M;
   double *lp = out->lppd ? out->lppd : (double *)malloc(nm * sizeof(double));
   double *pw = out->pwaic ? out->pwaic : (double *)malloc(nm * sizeof(double));
   int rc = (lp && pw) ? SR_OK : SR_ENOMEM;
   float ms = 0.0f;
-  if (!rc)
-    rc = post_rc(dev_form ? srw_waic_dev(device, stream, rec, off, n_sel, count, W, N, M, X, cd, cdw, manycd, lp,
-                                         out->ll_mean, pw, &ms)
-                          : srw_waic_host(device, ab_pi, n_sel, count, N, M, X, cd, cdw, manycd, lp, out->ll_mean, pw,
-                                          &ms));
+  if (!rc) rc = sr_code_of(srw_waic(v, N, M, ds->X, cd, cdw, manycd, lp, out->ll_mean, pw, &ms));
   if (!rc) {
     rc = sr_waic_reduce(N, M, lp, pw, out);
     out->kernel_ms = ms;
@@ -1693,11 +1683,14 @@ SR_API int sr_waic(const sr_dataset *ds, const int16_t *ab_pi, const double *cd,
   const int Mt = manycd ? ds->M : 1, cdw = manycd ? 2 * ds->M : 3;
   if (!waic_cd_ok(cd, (int32_t)((int64_t)n_sel * count), cdw, Mt)) return SR_EINVAL;
   if ((int64_t)ds->N * ds->M > WAIC_CELLS_MAX) return SR_EUNSUPPORTED;
-  if (!srw_waic_host) return SR_EUNSUPPORTED;
+  if (!srw_waic) return SR_EUNSUPPORTED;
   const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
   if (!rows) return SR_ENOMEM;
   for (int k = 0; k < n_sel; k++) rows[k] = cd + (size_t)k * count * cdw;
-  rc = waic_run(ds->N, ds->M, out, 0, device, NULL, NULL, NULL, 0, ab_pi, n_sel, count, ds->X, rows, cdw, manycd != 0);
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = waic_run(&v, ds, out, rows, cdw, manycd != 0);
+  sr_recview_release(&v);
   free(rows);
   return rc;
 }
@@ -1708,33 +1701,25 @@ SR_API int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, 
   if (!s || !chains) return SR_EINVAL;
   int rc = waic_check(out, n_sel, count, s->ds.N, s->ds.M);
   if (rc) return rc;
-  if (first < 0 || first > s->nrec || count > s->nrec - first) return SR_EINVAL;
-  for (int k = 0; k < n_sel; k++)
-    if (chains[k] < 0 || chains[k] >= s->nchains) return SR_EINVAL;
-  if ((int64_t)s->ds.N * s->ds.M > WAIC_CELLS_MAX) return SR_EUNSUPPORTED;
-  if (!srw_waic_dev) return SR_EUNSUPPORTED;
-  const int16_t *rec;
-  int cap, dev;
-  void *stream;
-  if (srk_records_device(s->dev, &rec, &cap, &dev, &stream)) return SR_EDEVICE;
+  sr_recview v;
+  rc = session_view(s, chains, n_sel, first, count,
+                    (int64_t)s->ds.N * s->ds.M > WAIC_CELLS_MAX || !srw_waic ? SR_EUNSUPPORTED : SR_OK, &v);
+  if (rc) return rc;
   const int M = s->ds.M, manycd = s->opts.manycd != 0;
   const int Mt = manycd ? M : 1, cdw = manycd ? 2 * M : 3;
-  const long long W = 2LL * M + s->ds.N;
   /* the rates come to the host through the fetch entry points (the int16 rows stay in HBM): every chain's
      per-taxon rows at once, or the chosen chains' (c, d, loglik) rows one chain at a time */
-  long long *off = (long long *)malloc(sizeof(long long) * n_sel);
   const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
   double *buf = (double *)malloc(sizeof(double) * (size_t)(manycd ? s->nchains : n_sel) * count * cdw);
-  rc = (off && rows && buf) ? SR_OK : SR_ENOMEM;
+  rc = (rows && buf) ? SR_OK : SR_ENOMEM;
   if (!rc && manycd && srk_fetch_cdv(s->dev, first, count, buf)) rc = SR_EDEVICE;
   for (int k = 0; k < n_sel && !rc; k++) {
-    off[k] = ((long long)chains[k] * cap + first) * W;
     rows[k] = buf + (size_t)(manycd ? chains[k] : k) * count * cdw;
     if (!manycd && srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, (double *)rows[k])) rc = SR_EDEVICE;
     if (!rc && !waic_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
   }
-  if (!rc) rc = waic_run(s->ds.N, M, out, 1, dev, stream, rec, off, W, NULL, n_sel, count, s->ds.X, rows, cdw, manycd);
-  free(off);
+  if (!rc) rc = waic_run(&v, &s->ds, out, rows, cdw, manycd);
+  sr_recview_release(&v);
   free(rows);
   free(buf);
   return rc;

@@ -1,6 +1,7 @@
 /*
  * sr_internal.h -- interface between the C host layer (sr_host.c) and the HIP device
- * layer (sr_device.hip).  Plain C.
+ * layer (sr_device.hip).  Plain C.  The analyses over saved records have their own
+ * interface, sr_records.h; srk_records_device is where the two meet.
  */
 #ifndef SR_INTERNAL_H
 #define SR_INTERNAL_H
@@ -108,72 +109,6 @@ int srk_upload_records(srk_dev *d, int count, const int16_t *ab_pi, const double
 /* the session's record buffer in HBM: [nchains][rec_cap][2M+N] int16 */
 int srk_records_device(srk_dev *d, const int16_t **rec, int *rec_cap, int *device, void **stream);
 
-/* posterior summaries (sr_post.hip); kinds = SR_POST_* bit positions */
-#define SRP_PAIR_ORDER 0
-#define SRP_ALIVE 1
-#define SRP_FALSE_ALIVE 2
-#define SRP_FALSE_ONES 3
-#define SRP_EXP_PI 4
-#define SRP_EXP_A 5
-int srp_posterior_dev(int device, void *stream, int kind, const int16_t *d_rec, const long long *chain_off, int n_sel,
-                      int count, long long row_stride, int N, int M, const uint8_t *X_host, int chains_selected,
-                      double *out_host, float *ms);
-int srp_posterior_host(int device, int kind, const int16_t *ab_pi, int n_sel, int count, int N, int M,
-                       const uint8_t *X_host, int chains_selected, double *out_host, float *ms);
-/* convergence diagnostics (sr_diag.hip): the exact integer moments of n_sel chains' records, two sequences of
-   h = count / 2 rows per chain (rows [0, h) and [count - h, count)), lags 0..L (1 <= L < h): host buffers
-   P, F, B [2 n_sel][L+1][W] and S1 [2 n_sel][W], W = 2M + N.  sr_host.c refers to both weakly: the host-only
-   builds (device layer stubbed) have neither, and sr_diagnostics returns SR_EUNSUPPORTED there. */
-int srd_moments_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
-                    long long row_stride, int W, int L, long long *P, long long *F, long long *B, long long *S1,
-                    float *ms);
-int srd_moments_host(int device, const int16_t *ab_pi, int n_sel, int count, int W, int L, long long *P, long long *F,
-                     long long *B, long long *S1, float *ms);
-/* posterior marginals (sr_marg.hip): the exact histograms of every record column over n_sel chains' `count` rows
-   (bins 0..N, a flagged chain's rows reflected) and what is read off them; flip [n_sel] (or NULL) and probs [Q]
-   (Q <= 16) are host inputs, hist [W][N+1], outside [W], pi_sum [n_sel][N], quant [Q][W], mode [W], mean [W] host
-   buffers, each optional.  Weak in sr_host.c like the moment kernels: sr_marginals returns SR_EUNSUPPORTED in
-   the host-only builds. */
-int srm_marginals_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
-                      long long row_stride, int N, int M, const uint8_t *flip, const double *probs, int Q,
-                      uint32_t *hist, uint32_t *outside, long long *pi_sum, int32_t *quant, int32_t *mode, double *mean,
-                      float *ms);
-int srm_marginals_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *flip,
-                       const double *probs, int Q, uint32_t *hist, uint32_t *outside, long long *pi_sum,
-                       int32_t *quant, int32_t *mode, double *mean, float *ms);
-/* taxon-pair relations, durations, richness (sr_rel.hip): exact counts over n_sel chains' `count` rows, a flagged
-   chain's limits reflected; flip [n_sel] (or NULL) is a host input, pair[4] (orig_before, ext_before, precedes,
-   overlap: [M][M] each), dur_hist [M][N+1], dur_outside [M], rich_hist [N][M+1] host buffers, each optional.  Weak
-   in sr_host.c like the marginals' entry points: sr_relations returns SR_EUNSUPPORTED in the host-only builds. */
-int srr_relations_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
-                      long long row_stride, int N, int M, const uint8_t *flip, uint32_t *const pair[4],
-                      uint32_t *dur_hist, uint32_t *dur_outside, uint32_t *rich_hist, float *ms);
-int srr_relations_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *flip,
-                       uint32_t *const pair[4], uint32_t *dur_hist, uint32_t *dur_outside, uint32_t *rich_hist,
-                       float *ms);
-/* WAIC's pointwise terms (sr_waic.hip): lppd, ll_mean, pwaic [N][M] over n_sel chains' `count` rows, summed in the
-   order include/seriation.h fixes.  X [N][M] and cd [n_sel] are host inputs: chain k's c, d rows [count][cdw],
-   c of taxon m at [m], d at [Mt + m], Mt = M when manycd and 1 otherwise (cdw 3 takes the (c, d, loglik) rows as
-   they are), every value already checked against the domain; lppd, pwaic and the optional ll_mean are host
-   buffers.  Weak in sr_host.c like the relations' entry points: sr_waic returns SR_EUNSUPPORTED in the host-only
-   builds. */
-int srw_waic_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
-                 long long row_stride, int N, int M, const uint8_t *X, const double *const *cd, int cdw, int manycd,
-                 double *lppd, double *ll_mean, double *pwaic, float *ms);
-int srw_waic_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *X,
-                  const double *const *cd, int cdw, int manycd, double *lppd, double *ll_mean, double *pwaic,
-                  float *ms);
-/* chain agreement (sr_agree.hip): pair_counts [n_sel][N][N], dist and dist_mirror [n_sel][n_sel] over n_sel chains'
-   `count` rows (only the pi part of a row is read), exact integers; host buffers, each optional.
-   sra_distances_host is the reduction alone, from pair counts in host memory (any uint32 values).  Weak in
-   sr_host.c like the relations' entry points: sr_agreement returns SR_EUNSUPPORTED in the host-only builds. */
-int sra_agreement_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel, int count,
-                      long long row_stride, int N, int M, uint32_t *pair_counts, long long *dist,
-                      long long *dist_mirror, float *ms);
-int sra_agreement_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, uint32_t *pair_counts,
-                       long long *dist, long long *dist_mirror, float *ms);
-int sra_distances_host(int device, int N, int n_sel, const uint32_t *pair_counts, long long *dist,
-                       long long *dist_mirror, float *ms);
 void srk_destroy(srk_dev *d);
 
 #ifdef __cplusplus

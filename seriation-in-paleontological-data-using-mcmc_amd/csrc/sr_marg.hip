@@ -26,6 +26,9 @@
  *
  * The columns are processed in batches whose device histogram stays below SRM_BATCH_BYTES; a batch reads only
  * its own columns, so every record entry is read once.
+ *
+ * The rows are addressed through a record view (sr_records.h: chain k's rows start at rec + chain_off[k], row_stride
+ * apart); srm_marginals is the unit's one entry point.  The cut of the stream and the pick of tc are sr_analysis.h's.
  */
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -33,14 +36,14 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "sr_internal.h"
+#include "sr_records.h"
+#include "sr_analysis.h"
 
 #define SRM_THREADS 512
 #define SRM_WAVES (SRM_THREADS / 64)
 #define SRM_SUM_THREADS 256              /* summary kernel: one wave per column */
 #define SRM_SUM_WAVES (SRM_SUM_THREADS / 64)
 #define SRM_U 16                         /* rows in flight per lane */
-#define SRM_LDS_MAX (160 * 1024)         /* all the LDS one workgroup can have; the kernels declare no static LDS */
 #define SRM_BATCH_BYTES ((size_t)256 << 20)   /* device histogram of one column batch (as DIAG_BATCH_BYTES) */
 #define SRM_MIN_ROWS 64                  /* rows of the sample stream a block takes at least */
 #define SRM_QMAX 16
@@ -192,36 +195,31 @@ __global__ __launch_bounds__(SRM_SUM_THREADS) void sr_marg_sum_kernel(MargSumArg
   }
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-  fprintf(stderr, "seriation: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); rc = -5; goto done; } } while (0)
-
-/* The marginals of n_sel chains' device-resident records.  flip [n_sel] and probs [Q] are host inputs (flip may be
+/* The marginals of the n_sel chains of a record view.  flip [n_sel] and probs [Q] are host inputs (flip may be
    NULL); hist [W][N+1], outside [W], pi_sum [n_sel][N], quant [Q][W], mode [W], mean [W] are host buffers, each
    optional. */
-extern "C" int srm_marginals_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel,
-                                 int count, long long row_stride, int N, int M, const uint8_t *flip,
-                                 const double *probs, int Q, uint32_t *hist, uint32_t *outside, long long *pi_sum,
-                                 int32_t *quant, int32_t *mode, double *mean, float *ms)
+extern "C" int srm_marginals(const sr_recview *v, int N, int M, const uint8_t *flip, const double *probs, int Q,
+                             uint32_t *hist, uint32_t *outside, long long *pi_sum, int32_t *quant, int32_t *mode,
+                             double *mean, float *ms)
 {
   int rc = 0;
-  long long *d_off = nullptr;
   uint8_t *d_flip = nullptr;
   unsigned *d_hist = nullptr, *d_outside = nullptr;
   unsigned long long *d_pisum = nullptr;
   int *d_quant = nullptr, *d_mode = nullptr;
   double *d_mean = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!d_rec || !chain_off || n_sel <= 0 || count < 1 || N < 1 || N > 32767 || M < 0 || Q < 0 || Q > SRM_QMAX ||
+  if (!v) return -1;
+  const int n_sel = v->n_sel, count = v->count;
+  hipStream_t st = (hipStream_t)v->stream;
+  if (!v->rec || !v->chain_off || n_sel <= 0 || count < 1 || N < 1 || N > 32767 || M < 0 || Q < 0 || Q > SRM_QMAX ||
       (Q > 0 && !probs) || (long long)n_sel * count >= (1LL << 31))
     return -1;
   if (ms) *ms = 0.0f;
   const int W = 2 * M + N, B = N + 1;
   const long long total = (long long)n_sel * count;
   const bool need_sum = (quant && Q > 0) || mode || mean;
-  int tcl = 6;
-  while (tcl > 0 && ((size_t)B << tcl) * sizeof(unsigned) > SRM_LDS_MAX) --tcl;
-  const int tc = 1 << tcl;
+  const int tcl = sr_lds_tile(B, 0, nullptr), tc = 1 << tcl;
   const size_t lds = ((size_t)B << tcl) * sizeof(unsigned);
   /* columns per batch: whole tiles, the device histogram within SRM_BATCH_BYTES */
   size_t cb = SRM_BATCH_BYTES / ((size_t)B * sizeof(unsigned));
@@ -230,11 +228,9 @@ extern "C" int srm_marginals_dev(int device, void *stream, const int16_t *d_rec,
   if (cb > (size_t)W) cb = W;
   {
     int ncu = 0, per_cu = 0;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, v->device));
     if (ncu < 1) ncu = 1;
-    HIPCHK(hipMalloc(&d_off, sizeof(long long) * n_sel));
-    HIPCHK(hipMemcpy(d_off, chain_off, sizeof(long long) * n_sel, hipMemcpyHostToDevice));
     if (flip) {
       HIPCHK(hipMalloc(&d_flip, n_sel));
       HIPCHK(hipMemcpy(d_flip, flip, n_sel, hipMemcpyHostToDevice));
@@ -257,16 +253,10 @@ extern "C" int srm_marginals_dev(int device, void *stream, const int16_t *d_rec,
     for (int col0 = 0; col0 < W; col0 += (int)cb) {
       const int ncol = W - col0 < (int)cb ? W - col0 : (int)cb;
       const int tiles = (ncol + tc - 1) / tc;
-      /* cut the sample stream into as many pieces as keep all blocks resident at once (one round, no tail),
-         SRM_MIN_ROWS rows per block at least */
-      long long ny = (long long)ncu * per_cu / tiles, nymax = total / SRM_MIN_ROWS;
-      if (ny > nymax) ny = nymax;
-      if (ny > 65535) ny = 65535;
-      if (ny < 1) ny = 1;
-      const long long rpy = (total + ny - 1) / ny;
-      ny = (total + rpy - 1) / rpy;
+      long long ny;
+      const long long rpy = sr_pieces((long long)ncu * per_cu, tiles, total, SRM_MIN_ROWS, SR_GRID_CAP, &ny);
       MargArgs A;
-      A.rec = d_rec; A.chain_off = d_off; A.row_stride = row_stride; A.flip = d_flip;
+      A.rec = v->rec; A.chain_off = v->chain_off; A.row_stride = v->row_stride; A.flip = d_flip;
       A.n_sel = n_sel; A.count = count; A.N = N; A.M = M;
       A.col0 = col0; A.ncol = ncol; A.tcl = tcl; A.total = total; A.rows_per_y = rpy;
       A.hist = d_hist; A.outside = d_outside; A.pi_sum = d_pisum;
@@ -299,7 +289,6 @@ extern "C" int srm_marginals_dev(int device, void *stream, const int16_t *d_rec,
 done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (d_off) (void)hipFree(d_off);
   if (d_flip) (void)hipFree(d_flip);
   if (d_hist) (void)hipFree(d_hist);
   if (d_outside) (void)hipFree(d_outside);
@@ -307,32 +296,5 @@ done:
   if (d_quant) (void)hipFree(d_quant);
   if (d_mode) (void)hipFree(d_mode);
   if (d_mean) (void)hipFree(d_mean);
-  return rc;
-}
-
-/* Records from host memory: ab_pi [n_sel][count][2M+N] int16 (selection order). */
-extern "C" int srm_marginals_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M,
-                                  const uint8_t *flip, const double *probs, int Q, uint32_t *hist, uint32_t *outside,
-                                  long long *pi_sum, int32_t *quant, int32_t *mode, double *mean, float *ms)
-{
-  int rc = 0;
-  int16_t *d_rec = nullptr;
-  long long *off = nullptr;
-  if (!ab_pi || n_sel <= 0 || count < 1 || N < 1 || M < 0) return -1;
-  const long long W = 2LL * M + N;
-  const size_t bytes = (size_t)n_sel * count * W * sizeof(int16_t);
-  off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return -4;
-  for (int k = 0; k < n_sel; ++k) off[k] = (long long)k * count * W;
-  {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_rec, bytes));
-    HIPCHK(hipMemcpy(d_rec, ab_pi, bytes, hipMemcpyHostToDevice));
-    rc = srm_marginals_dev(device, nullptr, d_rec, off, n_sel, count, W, N, M, flip, probs, Q, hist, outside, pi_sum,
-                           quant, mode, mean, ms);
-  }
-done:
-  if (d_rec) (void)hipFree(d_rec);
-  free(off);
   return rc;
 }

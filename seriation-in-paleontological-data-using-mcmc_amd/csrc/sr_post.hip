@@ -19,7 +19,8 @@
  *
  * Layout: samples are the sweep kernel's records, int16 rows [a (M) | b (M) | pi (N)] with
  * pi[site] = position (mcmc_save_chain, mcmc.c:69-92), one row per saved mcmc_sample call;
- * chain k's rows start at rec + chain_off[k], consecutive rows row_stride apart.  A block owns a
+ * the rows are addressed through a record view (sr_records.h): chain k's rows start at
+ * rec + chain_off[k], consecutive rows row_stride apart.  A block owns a
  * tile of 16 output rows x 64 output columns: lane = column (its operand loads coalesce across
  * the wave), each thread keeps 4 rows' accumulators in registers.  Operands are staged through
  * LDS in chunks of CS samples, the next chunk's loads in flight while the current one is summed;
@@ -31,7 +32,8 @@
 #include <stdint.h>
 #include <type_traits>
 #include <stdio.h>
-#include "sr_internal.h"
+#include "sr_records.h"
+#include "sr_analysis.h"
 
 #define TR 16   /* output rows per block (4 waves x 4 rows) */
 #define TCOL 64 /* output columns per block (lanes) */
@@ -168,20 +170,17 @@ __global__ __launch_bounds__(256) void sr_post_kernel(PostArgs P)
   }
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-  fprintf(stderr, "seriation: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); rc = -5; goto done; } } while (0)
-
-/* One summary kind over device-resident records; out_host receives R x C doubles. */
-extern "C" int srp_posterior_dev(int device, void *stream, int kind, const int16_t *d_rec, const long long *chain_off,
-                                 int n_sel, int count, long long row_stride, int N, int M, const uint8_t *X_host,
-                                 int chains_selected, double *out_host, float *ms)
+/* One summary kind over the view's records; out_host receives R x C doubles. */
+extern "C" int srp_posterior(const sr_recview *v, int kind, int N, int M, const uint8_t *X_host, int chains_selected,
+                             double *out_host, float *ms)
 {
   int rc = 0;
-  long long *d_off = nullptr;
   uint8_t *d_X = nullptr;
   double *d_out = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = (hipStream_t)stream;
+  if (!v) return -1;
+  const int n_sel = v->n_sel, count = v->count;
+  hipStream_t st = (hipStream_t)v->stream;
   int R, C;
   switch (kind) {
     case SRP_PAIR_ORDER: R = N; C = N; break;
@@ -194,16 +193,14 @@ extern "C" int srp_posterior_dev(int device, void *stream, int kind, const int16
   if ((long long)n_sel * count >= (1LL << 31)) return -1;   /* the kernel indexes samples in 32 bits */
   if (kind == SRP_FALSE_ONES && !X_host) return -1;
   {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_off, sizeof(long long) * n_sel));
-    HIPCHK(hipMemcpy(d_off, chain_off, sizeof(long long) * n_sel, hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(v->device));
     HIPCHK(hipMalloc(&d_out, sizeof(double) * (size_t)R * C));
     if (kind == SRP_FALSE_ONES) {
       HIPCHK(hipMalloc(&d_X, (size_t)N * M));
       HIPCHK(hipMemcpy(d_X, X_host, (size_t)N * M, hipMemcpyHostToDevice));
     }
     PostArgs A;
-    A.rec = d_rec; A.chain_off = d_off; A.row_stride = row_stride; A.X = d_X;
+    A.rec = v->rec; A.chain_off = v->chain_off; A.row_stride = v->row_stride; A.X = d_X;
     A.n_sel = n_sel; A.count = count; A.N = N; A.M = M; A.R = R; A.C = C;
     A.div = (double)chains_selected; A.out = d_out;
     dim3 grid((C + TCOL - 1) / TCOL, (R + TR - 1) / TR);
@@ -227,33 +224,7 @@ extern "C" int srp_posterior_dev(int device, void *stream, int kind, const int16
 done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (d_off) (void)hipFree(d_off);
   if (d_out) (void)hipFree(d_out);
   if (d_X) (void)hipFree(d_X);
-  return rc;
-}
-
-/* Records from host memory: ab_pi [n_sel][count][2M+N] int16 (selection order). */
-extern "C" int srp_posterior_host(int device, int kind, const int16_t *ab_pi, int n_sel, int count, int N, int M,
-                                  const uint8_t *X_host, int chains_selected, double *out_host, float *ms)
-{
-  int rc = 0;
-  int16_t *d_rec = nullptr;
-  long long *off = nullptr;
-  const long long W = 2LL * M + N;
-  const size_t bytes = (size_t)n_sel * count * W * sizeof(int16_t);
-  if (n_sel <= 0 || count < 0) return -1;
-  off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return -4;
-  for (int k = 0; k < n_sel; ++k) off[k] = (long long)k * count * W;
-  {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_rec, bytes + 16));
-    if (bytes) HIPCHK(hipMemcpy(d_rec, ab_pi, bytes, hipMemcpyHostToDevice));
-    rc = srp_posterior_dev(device, nullptr, kind, d_rec, off, n_sel, count, W, N, M, X_host, chains_selected, out_host, ms);
-  }
-done:
-  if (d_rec) (void)hipFree(d_rec);
-  free(off);
   return rc;
 }

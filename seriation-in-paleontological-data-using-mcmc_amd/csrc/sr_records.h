@@ -1,0 +1,95 @@
+/*
+ * sr_records.h -- the record view: how the analyses over saved records (posterior summaries, convergence
+ * diagnostics, marginals, taxon-pair relations, WAIC, chain agreement) address the rows they read, and those
+ * analyses' entry points.  Plain C.  Included by sr_host.c, sr_records.hip and the analysis .hip files only: the
+ * sweep kernel's sources (sr_device.hip, sr_internal.h; the snapshot sr_spec.c compiles from) know nothing of it.
+ */
+#ifndef SR_RECORDS_H
+#define SR_RECORDS_H
+#include <stdint.h>
+#include <stddef.h>
+
+/* A selection of record rows resident on a GPU: n_sel chains' `count` rows of int16 entries [a (M) | b (M) | pi (N)].
+   Row t of selected chain k starts at rec + chain_off[k] + t * row_stride; rec and chain_off are device pointers.
+   Chains [c0, c0 + n) of a view are a view again, with no allocation: sr_recview_chains. */
+typedef struct {
+  int device;
+  void *stream;                 /* hipStream_t the kernels are queued on (NULL: the default stream) */
+  const int16_t *rec;
+  const long long *chain_off;   /* [n_sel] element offsets; owned by the view */
+  int n_sel, count;
+  long long row_stride;
+  int owns_rec;                 /* 1: rec was uploaded by sr_recview_host and is freed with the view */
+} sr_recview;
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Every function below returns 0, -1 (invalid argument), -4 (out of host memory) or -5 (a HIP error, reported on
+   stderr); a view that was not built holds nothing to release. */
+
+/* records from host memory: ab_pi [n_sel][count][W] (selection order) uploaded to `device`, chain k at k * count * W;
+   count == 0 is a view of no rows */
+int sr_recview_host(sr_recview *v, int device, const int16_t *ab_pi, int n_sel, int count, long long W);
+/* records already on `device` (a session's buffer): only the offsets off [n_sel] (host memory) are uploaded */
+int sr_recview_device(sr_recview *v, int device, void *stream, const int16_t *d_rec, const long long *off, int n_sel,
+                      int count, long long row_stride);
+void sr_recview_release(sr_recview *v);
+
+/* chains [c0, c0 + n) of v: borrows everything, is not released */
+static inline sr_recview sr_recview_chains(const sr_recview *v, int c0, int n)
+{
+  sr_recview s = *v;
+  s.chain_off += c0;
+  s.n_sel = n;
+  s.owns_rec = 0;
+  return s;
+}
+
+/* The analyses: one entry point each, over a view.  Inputs other than the records and all outputs are host
+   memory; ms (optional) receives the kernels' time.  sr_host.c refers to all of them, and to the view's functions,
+   weakly: the host-only builds (device layer stubbed) have none and answer SR_EUNSUPPORTED. */
+
+/* posterior summaries (sr_post.hip): one kind (an SR_POST_* bit position) per call, out_host [R][C] */
+#define SRP_PAIR_ORDER 0
+#define SRP_ALIVE 1
+#define SRP_FALSE_ALIVE 2
+#define SRP_FALSE_ONES 3
+#define SRP_EXP_PI 4
+#define SRP_EXP_A 5
+int srp_posterior(const sr_recview *v, int kind, int N, int M, const uint8_t *X_host, int chains_selected,
+                  double *out_host, float *ms);
+/* convergence diagnostics (sr_diag.hip): the exact integer moments of the view's chains, two sequences of
+   h = count / 2 rows per chain (rows [0, h) and [count - h, count)), lags 0..L (1 <= L < h): P, F, B
+   [2 n_sel][L+1][W] and S1 [2 n_sel][W], W = 2M + N */
+int srd_moments(const sr_recview *v, int W, int L, long long *P, long long *F, long long *B, long long *S1, float *ms);
+/* posterior marginals (sr_marg.hip): the exact histograms of every record column (bins 0..N, a flagged chain's rows
+   reflected) and what is read off them; flip [n_sel] (or NULL) and probs [Q] (Q <= 16) are inputs, hist [W][N+1],
+   outside [W], pi_sum [n_sel][N], quant [Q][W], mode [W], mean [W] outputs, each optional */
+int srm_marginals(const sr_recview *v, int N, int M, const uint8_t *flip, const double *probs, int Q, uint32_t *hist,
+                  uint32_t *outside, long long *pi_sum, int32_t *quant, int32_t *mode, double *mean, float *ms);
+/* taxon-pair relations, durations, richness (sr_rel.hip): exact counts, a flagged chain's limits reflected; flip
+   [n_sel] (or NULL) is an input, pair[4] (orig_before, ext_before, precedes, overlap: [M][M] each), dur_hist
+   [M][N+1], dur_outside [M], rich_hist [N][M+1] outputs, each optional */
+int srr_relations(const sr_recview *v, int N, int M, const uint8_t *flip, uint32_t *const pair[4], uint32_t *dur_hist,
+                  uint32_t *dur_outside, uint32_t *rich_hist, float *ms);
+/* WAIC's pointwise terms (sr_waic.hip): lppd, ll_mean (optional), pwaic [N][M], summed in the order
+   include/seriation.h fixes.  X [N][M] and cd [n_sel] are inputs: chain k's c, d rows [count][cdw], c of taxon m at
+   [m], d at [Mt + m], Mt = M when manycd and 1 otherwise (cdw 3 takes the (c, d, loglik) rows as they are), every
+   value already checked against the domain */
+int srw_waic(const sr_recview *v, int N, int M, const uint8_t *X, const double *const *cd, int cdw, int manycd,
+             double *lppd, double *ll_mean, double *pwaic, float *ms);
+/* chain agreement (sr_agree.hip): pair_counts [n_sel][N][N], dist and dist_mirror [n_sel][n_sel] (only the pi part of
+   a row is read), exact integers, each optional.  sra_distances_host is the reduction alone, from pair counts in
+   host memory (any uint32 values): it reads no records and takes no view. */
+int sra_agreement(const sr_recview *v, int N, int M, uint32_t *pair_counts, long long *dist, long long *dist_mirror,
+                  float *ms);
+int sra_distances_host(int device, int N, int n_sel, const uint32_t *pair_counts, long long *dist,
+                       long long *dist_mirror, float *ms);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

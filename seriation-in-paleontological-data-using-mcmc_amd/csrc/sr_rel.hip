@@ -37,12 +37,17 @@
  * power of two (at most 64) whose bins fit the 160 KB of a workgroup; when not even one position's M + 1 bins fit
  * (M > 40000 or so) the waves add straight into the device histogram.  Every tile reads all the limits again, so
  * the pass costs N / tc readings of the records: one or a few for the shapes of the bench matrix.
+ *
+ * The rows are addressed through a record view (sr_records.h: chain k's rows start at rec + chain_off[k], row_stride
+ * apart); srr_relations is the unit's one entry point.  The cut of the stream into pieces and the pick of tc are
+ * sr_analysis.h's, shared with the marginals and the agreement.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "sr_internal.h"
+#include "sr_records.h"
+#include "sr_analysis.h"
 
 #define SRR_TILE 64                      /* pair kernel: the tile is SRR_TILE x SRR_TILE pairs */
 #define SRR_PWAVES 4
@@ -52,7 +57,6 @@
 #define SRR_THREADS 512                  /* duration and richness kernels */
 #define SRR_WAVES (SRR_THREADS / 64)
 #define SRR_U 8                          /* duration kernel: rows in flight per lane */
-#define SRR_LDS_MAX (160 * 1024)
 #define SRR_MIN_ROWS 64                  /* rows of the sample stream a block takes at least */
 
 struct RelArgs {
@@ -220,36 +224,19 @@ __global__ __launch_bounds__(SRR_THREADS) void sr_rel_rich_kernel(RelArgs A)
   }
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-  fprintf(stderr, "seriation: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); rc = -5; goto done; } } while (0)
-
-/* the sample stream cut into as many pieces as keep `resident` blocks busy in one round over `tiles` tiles,
-   SRR_MIN_ROWS rows per piece at least: rows per piece (*ny pieces) */
-static int srr_pieces(long long resident, long long tiles, int total, int *ny)
-{
-  long long n = resident / tiles, nmax = total / SRR_MIN_ROWS;
-  if (n > nmax) n = nmax;
-  if (n > 65535) n = 65535;
-  if (n < 1) n = 1;
-  const int rpp = (int)((total + n - 1) / n);
-  *ny = (total + rpp - 1) / rpp;
-  return rpp;
-}
-
-/* The relations of n_sel chains' device-resident records.  flip [n_sel] is a host input (may be NULL); pair[4]
+/* The relations of the n_sel chains of a record view.  flip [n_sel] is a host input (may be NULL); pair[4]
    ([M][M] each), dur_hist [M][N+1], dur_outside [M], rich_hist [N][M+1] are host buffers, each optional. */
-extern "C" int srr_relations_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel,
-                                 int count, long long row_stride, int N, int M, const uint8_t *flip,
-                                 uint32_t *const pair[4], uint32_t *dur_hist, uint32_t *dur_outside,
-                                 uint32_t *rich_hist, float *ms)
+extern "C" int srr_relations(const sr_recview *v, int N, int M, const uint8_t *flip, uint32_t *const pair[4],
+                             uint32_t *dur_hist, uint32_t *dur_outside, uint32_t *rich_hist, float *ms)
 {
   int rc = 0;
-  long long *d_off = nullptr;
   uint8_t *d_flip = nullptr;
   unsigned *d_pair[4] = {nullptr, nullptr, nullptr, nullptr}, *d_dur = nullptr, *d_out = nullptr, *d_rich = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!d_rec || !chain_off || !pair || n_sel <= 0 || count < 1 || N < 1 || N > 32767 || M < 1 ||
+  if (!v) return -1;
+  const int n_sel = v->n_sel, count = v->count;
+  hipStream_t st = (hipStream_t)v->stream;
+  if (!v->rec || !v->chain_off || !pair || n_sel <= 0 || count < 1 || N < 1 || N > 32767 || M < 1 ||
       (long long)n_sel * count >= (1LL << 31))
     return -1;
   if (ms) *ms = 0.0f;
@@ -260,11 +247,9 @@ extern "C" int srr_relations_dev(int device, void *stream, const int16_t *d_rec,
   const size_t rich_bytes = (size_t)N * ((size_t)M + 1) * sizeof(unsigned);
   {
     int ncu = 0, per_cu = 0;
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    HIPCHK(hipSetDevice(v->device));
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, v->device));
     if (ncu < 1) ncu = 1;
-    HIPCHK(hipMalloc(&d_off, sizeof(long long) * n_sel));
-    HIPCHK(hipMemcpy(d_off, chain_off, sizeof(long long) * n_sel, hipMemcpyHostToDevice));
     if (flip) {
       HIPCHK(hipMalloc(&d_flip, n_sel));
       HIPCHK(hipMemcpy(d_flip, flip, n_sel, hipMemcpyHostToDevice));
@@ -277,54 +262,55 @@ extern "C" int srr_relations_dev(int device, void *stream, const int16_t *d_rec,
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
     RelArgs A;
-    A.rec = d_rec; A.chain_off = d_off; A.row_stride = row_stride; A.flip = d_flip;
+    A.rec = v->rec; A.chain_off = v->chain_off; A.row_stride = v->row_stride; A.flip = d_flip;
     A.count = count; A.N = N; A.M = M; A.total = total;
     HIPCHK(hipEventRecord(e0, st));
     if (want_pair) {
       const int nt = (M + SRR_TILE - 1) / SRR_TILE;
-      int ny;
+      long long ny;
       HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sr_rel_pair_kernel, SRR_PTHREADS, 0));
       if (per_cu < 1) per_cu = 1;
-      A.rows_per_piece = srr_pieces((long long)ncu * per_cu, (long long)nt * nt, total, &ny);
+      A.rows_per_piece = (int)sr_pieces((long long)ncu * per_cu, (long long)nt * nt, total, SRR_MIN_ROWS, SR_GRID_CAP, &ny);
       A.tcl = 0; A.direct = 0; A.hist = nullptr; A.outside = nullptr;
       for (int q = 0; q < 4; ++q) {
         A.pair[q] = d_pair[q];
         if (d_pair[q]) HIPCHK(hipMemsetAsync(d_pair[q], 0, mm, st));
       }
-      hipLaunchKernelGGL(sr_rel_pair_kernel, dim3(nt, nt, ny), dim3(SRR_PTHREADS), 0, st, A);
+      hipLaunchKernelGGL(sr_rel_pair_kernel, dim3(nt, nt, (unsigned)ny), dim3(SRR_PTHREADS), 0, st, A);
       HIPCHK(hipGetLastError());
     }
     for (int q = 0; q < 4; ++q) A.pair[q] = nullptr;
     if (want_dur) {
-      int tcl = 6, ny;
-      while (tcl > 0 && ((size_t)(N + 1) << tcl) * sizeof(unsigned) > SRR_LDS_MAX) --tcl;
+      const int tcl = sr_lds_tile((size_t)N + 1, 0, nullptr);
+      long long ny;
       const size_t lds = ((size_t)(N + 1) << tcl) * sizeof(unsigned);
       const int tiles = (M + (1 << tcl) - 1) >> tcl;
       HIPCHK(hipFuncSetAttribute((const void *)sr_rel_dur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sr_rel_dur_kernel, SRR_THREADS, lds));
       if (per_cu < 1) per_cu = 1;
-      A.rows_per_piece = srr_pieces((long long)ncu * per_cu, tiles, total, &ny);
+      A.rows_per_piece = (int)sr_pieces((long long)ncu * per_cu, tiles, total, SRR_MIN_ROWS, SR_GRID_CAP, &ny);
       A.tcl = tcl; A.direct = 0; A.hist = d_dur; A.outside = d_out;
       if (d_dur) HIPCHK(hipMemsetAsync(d_dur, 0, dur_bytes, st));
       HIPCHK(hipMemsetAsync(d_out, 0, sizeof(unsigned) * M, st));
-      hipLaunchKernelGGL(sr_rel_dur_kernel, dim3(tiles, ny), dim3(SRR_THREADS), lds, st, A);
+      hipLaunchKernelGGL(sr_rel_dur_kernel, dim3(tiles, (unsigned)ny), dim3(SRR_THREADS), lds, st, A);
       HIPCHK(hipGetLastError());
     }
     if (rich_hist) {
       const size_t wd = SRR_WAVES * 64 * sizeof(int);
-      int tcl = 6, ny;
-      while (tcl > 0 && wd + (((size_t)M + 1) << tcl) * sizeof(unsigned) > SRR_LDS_MAX) --tcl;
-      const int direct = wd + (((size_t)M + 1) << tcl) * sizeof(unsigned) > SRR_LDS_MAX;
+      int fits;
+      int tcl = sr_lds_tile((size_t)M + 1, wd, &fits);
+      long long ny;
+      const int direct = !fits;
       if (direct) tcl = 6;
       const size_t lds = wd + (direct ? 0 : (((size_t)M + 1) << tcl) * sizeof(unsigned));
       const int tiles = (N + (1 << tcl) - 1) >> tcl;
       HIPCHK(hipFuncSetAttribute((const void *)sr_rel_rich_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sr_rel_rich_kernel, SRR_THREADS, lds));
       if (per_cu < 1) per_cu = 1;
-      A.rows_per_piece = srr_pieces((long long)ncu * per_cu, tiles, total, &ny);
+      A.rows_per_piece = (int)sr_pieces((long long)ncu * per_cu, tiles, total, SRR_MIN_ROWS, SR_GRID_CAP, &ny);
       A.tcl = tcl; A.direct = direct; A.hist = d_rich; A.outside = nullptr;
       HIPCHK(hipMemsetAsync(d_rich, 0, rich_bytes, st));
-      hipLaunchKernelGGL(sr_rel_rich_kernel, dim3(tiles, ny), dim3(SRR_THREADS), lds, st, A);
+      hipLaunchKernelGGL(sr_rel_rich_kernel, dim3(tiles, (unsigned)ny), dim3(SRR_THREADS), lds, st, A);
       HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(e1, st));
@@ -339,39 +325,11 @@ extern "C" int srr_relations_dev(int device, void *stream, const int16_t *d_rec,
 done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (d_off) (void)hipFree(d_off);
   if (d_flip) (void)hipFree(d_flip);
   for (int q = 0; q < 4; ++q)
     if (d_pair[q]) (void)hipFree(d_pair[q]);
   if (d_dur) (void)hipFree(d_dur);
   if (d_out) (void)hipFree(d_out);
   if (d_rich) (void)hipFree(d_rich);
-  return rc;
-}
-
-/* Records from host memory: ab_pi [n_sel][count][2M+N] int16 (selection order). */
-extern "C" int srr_relations_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M,
-                                  const uint8_t *flip, uint32_t *const pair[4], uint32_t *dur_hist,
-                                  uint32_t *dur_outside, uint32_t *rich_hist, float *ms)
-{
-  int rc = 0;
-  int16_t *d_rec = nullptr;
-  long long *off = nullptr;
-  if (!ab_pi || n_sel <= 0 || count < 1 || N < 1 || M < 1) return -1;
-  const long long W = 2LL * M + N;
-  const size_t bytes = (size_t)n_sel * count * W * sizeof(int16_t);
-  off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return -4;
-  for (int k = 0; k < n_sel; ++k) off[k] = (long long)k * count * W;
-  {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_rec, bytes));
-    HIPCHK(hipMemcpy(d_rec, ab_pi, bytes, hipMemcpyHostToDevice));
-    rc = srr_relations_dev(device, nullptr, d_rec, off, n_sel, count, W, N, M, flip, pair, dur_hist, dur_outside,
-                           rich_hist, ms);
-  }
-done:
-  if (d_rec) (void)hipFree(d_rec);
-  free(off);
   return rc;
 }

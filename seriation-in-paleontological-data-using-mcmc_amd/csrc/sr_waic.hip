@@ -24,12 +24,16 @@
  * rows (table of at most as much) and the order of the adds does not depend on the batching.  The first pass sums
  * p and l; the combine kernel adds a group's partials to the totals in chain order; the finish kernel forms
  * lppd = log(Sp / T) and mu = Sl / T; the second pass, the same kernel, sums (l - mu)^2 and stages only l[4].
+ *
+ * The rows are addressed through a record view (sr_records.h: chain k's rows start at rec + chain_off[k], row_stride
+ * apart); srw_waic is the unit's one entry point.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include "sr_internal.h"
+#include "sr_records.h"
+#include "sr_analysis.h"
 #include "sr_math.h"
 
 #define SRW_TILE 64                      /* taxa per workgroup: one per lane */
@@ -165,9 +169,6 @@ __global__ void sr_waic_finish_kernel(double *v0, double *v1, int which, double 
   }
 }
 
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-  fprintf(stderr, "seriation: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); rc = -5; goto done; } } while (0)
-
 static long long srw_scratch(void)
 {
   const char *e = getenv("SR_WAIC_SCRATCH");
@@ -175,21 +176,20 @@ static long long srw_scratch(void)
   return v > 0 ? v : SRW_SCRATCH_DEFAULT;
 }
 
-/* WAIC's pointwise terms of n_sel chains' device-resident records.  X [N][M] and cd [n_sel] (each chain's
+/* WAIC's pointwise terms of the n_sel chains of a record view.  X [N][M] and cd [n_sel] (each chain's
    [count][cdw] rows: c at [m], d at [Mt + m], Mt = M when manycd, else 1) are host inputs, already checked;
    lppd, ll_mean (may be NULL), pwaic [N][M] are host buffers. */
-extern "C" int srw_waic_dev(int device, void *stream, const int16_t *d_rec, const long long *chain_off, int n_sel,
-                            int count, long long row_stride, int N, int M, const uint8_t *X,
-                            const double *const *cd, int cdw, int manycd, double *lppd, double *ll_mean,
-                            double *pwaic, float *ms)
+extern "C" int srw_waic(const sr_recview *v, int N, int M, const uint8_t *X, const double *const *cd, int cdw,
+                        int manycd, double *lppd, double *ll_mean, double *pwaic, float *ms)
 {
   int rc = 0;
-  long long *d_off = nullptr;
   uint8_t *d_X = nullptr;
   double *d_cd = nullptr, *d_tab = nullptr, *d_part = nullptr, *d_tot = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  if (!d_rec || !chain_off || !X || !cd || !lppd || !pwaic || n_sel <= 0 || count < 1 || N < 1 || N > 32767 ||
+  if (!v) return -1;
+  const int n_sel = v->n_sel, count = v->count;
+  hipStream_t st = (hipStream_t)v->stream;
+  if (!v->rec || !v->chain_off || !X || !cd || !lppd || !pwaic || n_sel <= 0 || count < 1 || N < 1 || N > 32767 ||
       M < 1 || (long long)n_sel * count >= (1LL << 31) || (long long)n_sel * count < 2 ||
       (long long)N * M > (1LL << 27))
     return -1;
@@ -210,9 +210,7 @@ extern "C" int srw_waic_dev(int device, void *stream, const int16_t *d_rec, cons
   const unsigned nmb = (unsigned)((nm + 255) / 256);
   float total_ms = 0.0f;
   {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_off, sizeof(long long) * n_sel));
-    HIPCHK(hipMemcpy(d_off, chain_off, sizeof(long long) * n_sel, hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(v->device));
     HIPCHK(hipMalloc(&d_X, nm));
     HIPCHK(hipMemcpy(d_X, X, nm, hipMemcpyHostToDevice));
     HIPCHK(hipMalloc(&d_cd, sizeof(double) * G * RB * cdw));
@@ -223,7 +221,7 @@ extern "C" int srw_waic_dev(int device, void *stream, const int16_t *d_rec, cons
     HIPCHK(hipEventCreate(&e1));
     HIPCHK(hipMemsetAsync(d_tot, 0, sizeof(double) * 3 * nm, st));
     WaicArgs A;
-    A.rec = d_rec; A.chain_off = d_off; A.row_stride = row_stride; A.X = d_X; A.tab = d_tab;
+    A.rec = v->rec; A.chain_off = v->chain_off; A.row_stride = v->row_stride; A.X = d_X; A.tab = d_tab;
     A.mu = d_tot + nm; A.N = N; A.M = M;
     for (int pass = 1; pass <= 2; ++pass) {
       A.acc0 = d_part;
@@ -281,37 +279,10 @@ extern "C" int srw_waic_dev(int device, void *stream, const int16_t *d_rec, cons
 done:
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
-  if (d_off) (void)hipFree(d_off);
   if (d_X) (void)hipFree(d_X);
   if (d_cd) (void)hipFree(d_cd);
   if (d_tab) (void)hipFree(d_tab);
   if (d_part) (void)hipFree(d_part);
   if (d_tot) (void)hipFree(d_tot);
-  return rc;
-}
-
-/* Records from host memory: ab_pi [n_sel][count][2M+N] int16 (selection order). */
-extern "C" int srw_waic_host(int device, const int16_t *ab_pi, int n_sel, int count, int N, int M, const uint8_t *X,
-                             const double *const *cd, int cdw, int manycd, double *lppd, double *ll_mean,
-                             double *pwaic, float *ms)
-{
-  int rc = 0;
-  int16_t *d_rec = nullptr;
-  long long *off = nullptr;
-  if (!ab_pi || n_sel <= 0 || count < 1 || N < 1 || M < 1) return -1;
-  const long long W = 2LL * M + N;
-  const size_t bytes = (size_t)n_sel * count * W * sizeof(int16_t);
-  off = (long long *)malloc(sizeof(long long) * n_sel);
-  if (!off) return -4;
-  for (int k = 0; k < n_sel; ++k) off[k] = (long long)k * count * W;
-  {
-    HIPCHK(hipSetDevice(device));
-    HIPCHK(hipMalloc(&d_rec, bytes));
-    HIPCHK(hipMemcpy(d_rec, ab_pi, bytes, hipMemcpyHostToDevice));
-    rc = srw_waic_dev(device, nullptr, d_rec, off, n_sel, count, W, N, M, X, cd, cdw, manycd, lppd, ll_mean, pwaic, ms);
-  }
-done:
-  if (d_rec) (void)hipFree(d_rec);
-  free(off);
   return rc;
 }

@@ -40,19 +40,6 @@ int srk_records_device(srk_dev *d, const int16_t **rec, int *cap, int *dev, void
   (void)d; (void)rec; (void)cap; (void)dev; (void)stream;
   return -5;
 }
-int srp_posterior_dev(int device, void *stream, int kind, const int16_t *d_rec, const long long *off, int n_sel, int count,
-                      long long row_stride, int N, int M, const uint8_t *X, int cs, double *out, float *ms)
-{
-  (void)device; (void)stream; (void)kind; (void)d_rec; (void)off; (void)n_sel; (void)count; (void)row_stride;
-  (void)N; (void)M; (void)X; (void)cs; (void)out; (void)ms;
-  return -5;
-}
-int srp_posterior_host(int device, int kind, const int16_t *ab, int n_sel, int count, int N, int M, const uint8_t *X,
-                       int cs, double *out, float *ms)
-{
-  (void)device; (void)kind; (void)ab; (void)n_sel; (void)count; (void)N; (void)M; (void)X; (void)cs; (void)out; (void)ms;
-  return -5;
-}
 void srk_destroy(srk_dev *d) { (void)d; }
 int srk_fetch_cdv(srk_dev *d, int f, int c, double *v) { (void)d; (void)f; (void)c; (void)v; return -5; }
 int srk_copy_chain_records(srk_dev *d, int ch, int f, int c, int16_t *a, double *x)
