@@ -469,6 +469,64 @@ int sr_agreement_distances(int32_t N, int32_t n_sel, const uint32_t *pair_counts
 int sr_agreement_modes(int32_t n, const int64_t *dist, const int64_t *dist_mirror, int64_t scale, double threshold,
                        int32_t *mode, uint8_t *flip, int32_t *medoid, int32_t *size, int32_t *n_modes);
 
+/* ---- the central sampled state: the saved record with the smallest posterior expected loss: exact integers ----
+ * (an extension: every other summary is marginal -- a vector of means is not a permutation and per-column medians
+ * need not satisfy a <= b -- while the medoid of the draws is one coherent (pi, a, b) the sampler produced.)
+ * Records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position, n_sel chains (selection order) of
+ * `count` rows, T = n_sel * count.  flip [n_sel] (NULL = none) reflects a flagged chain's rows first, exactly as
+ * sr_marginals does: a' = N - b, b' = N - a, pi' = N - 1 - pi.  All arithmetic on record values is int32: any int16
+ * input is legal and nothing wraps.
+ *   pair_counts [N][N] uint32      C[i][j]: the number of the T rows with pi'(i) < pi'(j), pooled over the chains;
+ *                                  the diagonal is 0; both orders are counted, not derived (host records may tie)
+ *   order_loss [n_sel][count] int64  of row r: the sum over i < j of [pi'_r(i) < pi'_r(j)] C[j][i] +
+ *                                  [pi'_r(i) > pi'_r(j)] C[i][j]: the (row, pair) combinations that strictly order a
+ *                                  pair opposite to r; a tie in r adds 0; for permutation rows the sum of r's
+ *                                  Kendall-tau distances to all T rows.  Fewer than 2^29 pairs and counts below 2^32:
+ *                                  below 2^61
+ *   limit_loss [n_sel][count] int64  of row r: the sum over taxa m and all T rows s of |A_r[m] - A_s[m]| +
+ *                                  |B_r[m] - B_s[m]|, A = clamp(a', 0, N), B = clamp(b', 0, N): defined for any input
+ *   best [n_sel] int32             per chain k the row t that minimises (order_loss, limit_loss, t) within the chain
+ *   central_chain, central_row     the (k, t) that minimises (order_loss, limit_loss, k, t) lexicographically: k in
+ *                                  selection order, t within the rows given
+ *   state [2M+N] int32             the central row as [a | b | pi], reflected if its chain is flagged, not clamped
+ *   scale = T N (N - 1) / 2        as sr_agree_out.scale with T rows: order_loss / scale is the expected normalised
+ *                                  Kendall distance from the row to a posterior draw
+ * Exact integers: the result does not depend on the order of the adds.  order_loss, limit_loss, pair_counts, best and
+ * state are optional (NULL = skip); the scalars are always written.
+ * sr_order_loss is the order loss alone, of the given rows against counts the caller holds (against [N][N], any
+ * uint32 values, read as C above; e.g. the pooled counts of another mode, or sr_agreement's per-chain pair_counts
+ * summed), as sr_agreement_distances is to sr_agreement.
+ * SR_EINVAL: a NULL ds, ab_pi, out (sr_order_loss: against, order_loss), n_sel <= 0, count < 1, T >= 2^31, N outside
+ * 1..32767, M < 1, 2 M N T >= 2^62 (the limit loss would not fit; not for sr_order_loss); the session form also for
+ * rows beyond the buffered records or a chain index out of range.  SR_EUNSUPPORTED: a requested pair_counts larger
+ * than 1 GiB (N > 16384), or a library built without the device layer.  All reported before any device call, the
+ * outputs untouched.  Device scratch is bounded: the site pairs are taken in bands of at most SR_CENTRAL_SCRATCH
+ * bytes of counts (environment, read at each call, default 256 MiB; one row of 64-site tiles at least) and the limit
+ * columns in batches whose histogram and table stay within the same bound (one column at least); the results do not
+ * depend on it. */
+typedef struct {
+  const uint8_t *flip;           /* in: [n_sel] or NULL */
+  int64_t *order_loss;           /* out: [n_sel][count], NULL = skip */
+  int64_t *limit_loss;           /* out: [n_sel][count] */
+  uint32_t *pair_counts;         /* out: [N][N] pooled, oriented */
+  int32_t *best;                 /* out: [n_sel] */
+  int32_t *state;                /* out: [2M+N] */
+  int32_t central_chain, central_row;   /* out: selection order, row within the view */
+  int64_t scale;                 /* out */
+  double kernel_ms;              /* out */
+} sr_central_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M */
+int sr_central(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+               sr_central_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order), on the session's
+   stream; the session's state and records are left untouched */
+int sr_session_central(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                       sr_central_out *out);
+/* the order loss alone, against any counts: against [N][N] any uint32, order_loss [n_sel][count]; kernel_ms optional */
+int sr_order_loss(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, const uint8_t *flip,
+                  const uint32_t *against, int32_t device, int64_t *order_loss, double *kernel_ms);
+
 const char *sr_strerror(int code);
 int sr_device_count(void);
 const char *sr_version(void);

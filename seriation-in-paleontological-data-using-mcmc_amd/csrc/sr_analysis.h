@@ -1,6 +1,6 @@
 /*
  * sr_analysis.h -- what the host code of the analysis units shares.  HIP only: included by sr_records.hip and the
- * six analysis .hip files (sr_post, sr_diag, sr_marg, sr_rel, sr_waic, sr_agree), by nothing else.
+ * seven analysis .hip files (sr_post, sr_diag, sr_marg, sr_rel, sr_waic, sr_agree, sr_central), by nothing else.
  */
 #ifndef SR_ANALYSIS_H
 #define SR_ANALYSIS_H

@@ -1051,7 +1051,7 @@ static double *post_slot(sr_posterior_out *o, int k)
 
 /* ---- the record view of the analyses below (sr_records.h) ---- */
 /* The view's functions (sr_records.hip) and the analyses' entry points (sr_post, sr_diag, sr_marg, sr_rel, sr_agree,
-   sr_waic .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
+   sr_waic, sr_central .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
    every analysis reports SR_EUNSUPPORTED, after its argument checks and before anything is uploaded. */
 #define SR_WEAK(f) extern __typeof__(f) f __attribute__((weak))
 SR_WEAK(sr_recview_host);
@@ -1064,6 +1064,8 @@ SR_WEAK(srr_relations);
 SR_WEAK(sra_agreement);
 SR_WEAK(sra_distances_host);
 SR_WEAK(srw_waic);
+SR_WEAK(src_central);
+SR_WEAK(src_order_loss);
 
 /* the device layer's return code (0, -1, -4, anything else) as an SR_* code */
 static int sr_code_of(int rc) { return rc == 0 ? SR_OK : (rc == -1 ? SR_EINVAL : (rc == -4 ? SR_ENOMEM : SR_EDEVICE)); }
@@ -1589,6 +1591,85 @@ SR_API int sr_agreement_modes(int32_t n, const int64_t *dist, const int64_t *dis
   if (n_modes) *n_modes = g;
   free(queue); free(seen); free(fl);
   return SR_OK;
+}
+
+/* ---- the central sampled state: the record of smallest expected loss (definitions: include/seriation.h) ---- */
+/* the argument checks all three entry points share, made before any device call */
+static int central_check_shape(int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (n_sel <= 0 || count < 1 || (int64_t)n_sel * count >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  return SR_OK;
+}
+
+static int central_check(const sr_central_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (!out) return SR_EINVAL;
+  const int rc = central_check_shape(n_sel, count, N, M);
+  if (rc) return rc;
+  /* the limit loss: 2M columns, |difference| <= N, T rows */
+  if ((unsigned __int128)2 * M * N * ((int64_t)n_sel * count) >= ((unsigned __int128)1 << 62)) return SR_EINVAL;
+  if (out->pair_counts && (int64_t)N * N > REL_OUT_MAX) return SR_EUNSUPPORTED;
+  return SR_OK;
+}
+
+static int central_run(const sr_recview *v, const sr_dataset *ds, sr_central_out *out)
+{
+  float ms = 0.0f;
+  int32_t chain = 0, row = 0;
+  const int rc = src_central(v, ds->N, ds->M, out->flip, (long long *)out->order_loss, (long long *)out->limit_loss,
+                             out->pair_counts, out->best, out->state, &chain, &row, &ms);
+  if (!rc) {
+    out->central_chain = chain;
+    out->central_row = row;
+    out->scale = (int64_t)v->n_sel * v->count * ((int64_t)ds->N * (ds->N - 1) / 2);
+    out->kernel_ms = ms;
+  }
+  return sr_code_of(rc);
+}
+
+SR_API int sr_central(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                      sr_central_out *out)
+{
+  if (!ds || !ab_pi) return SR_EINVAL;
+  int rc = central_check(out, n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!src_central) return SR_EUNSUPPORTED;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = central_run(&v, ds, out);
+  sr_recview_release(&v);
+  return rc;
+}
+
+SR_API int sr_session_central(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                              sr_central_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = central_check(out, n_sel, count, s->ds.N, s->ds.M);
+  if (rc == SR_EINVAL) return rc;
+  sr_recview v;   /* an invalid selection wins over an output too large */
+  rc = session_view(s, chains, n_sel, first, count, rc ? rc : (src_central ? SR_OK : SR_EUNSUPPORTED), &v);
+  if (rc) return rc;
+  rc = central_run(&v, &s->ds, out);
+  sr_recview_release(&v);
+  return rc;
+}
+
+SR_API int sr_order_loss(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, const uint8_t *flip,
+                         const uint32_t *against, int32_t device, int64_t *order_loss, double *kernel_ms)
+{
+  if (!ds || !ab_pi || !against || !order_loss) return SR_EINVAL;
+  int rc = central_check_shape(n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!src_order_loss) return SR_EUNSUPPORTED;
+  sr_recview v;
+  float ms = 0.0f;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = sr_code_of(src_order_loss(&v, ds->N, ds->M, flip, against, (long long *)order_loss, &ms));
+  if (!rc && kernel_ms) *kernel_ms = ms;
+  sr_recview_release(&v);
+  return rc;
 }
 
 /* ---- WAIC and the pointwise model fit (definitions: include/seriation.h) ---- */

@@ -1,6 +1,6 @@
 /*
  * sr_records.h -- the record view: how the analyses over saved records (posterior summaries, convergence
- * diagnostics, marginals, taxon-pair relations, WAIC, chain agreement) address the rows they read, and those
+ * diagnostics, marginals, taxon-pair relations, WAIC, chain agreement, the central state) address the rows they read, and those
  * analyses' entry points.  Plain C.  Included by sr_host.c, sr_records.hip and the analysis .hip files only: the
  * sweep kernel's sources (sr_device.hip, sr_internal.h; the snapshot sr_spec.c compiles from) know nothing of it.
  */
@@ -87,6 +87,15 @@ int sra_agreement(const sr_recview *v, int N, int M, uint32_t *pair_counts, long
                   float *ms);
 int sra_distances_host(int device, int N, int n_sel, const uint32_t *pair_counts, long long *dist,
                        long long *dist_mirror, float *ms);
+
+/* the central sampled state (sr_central.hip): flip [n_sel] (or NULL) is an input; order_loss, limit_loss
+   [n_sel][count], pair_counts [N][N] (pooled, oriented), best [n_sel], state [2M+N] outputs, each optional; *chain and
+   *row the central row's.  src_order_loss is the order loss alone against counts in host memory (against [N][N], any
+   uint32 values). */
+int src_central(const sr_recview *v, int N, int M, const uint8_t *flip, long long *order_loss, long long *limit_loss,
+                uint32_t *pair_counts, int32_t *best, int32_t *state, int32_t *chain, int32_t *row, float *ms);
+int src_order_loss(const sr_recview *v, int N, int M, const uint8_t *flip, const uint32_t *against,
+                   long long *order_loss, float *ms);
 
 #ifdef __cplusplus
 }

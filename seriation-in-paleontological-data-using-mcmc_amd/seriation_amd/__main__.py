@@ -8,6 +8,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
                                     [--marginals] [--relations] [--waic] [--modes [--mode-threshold X]]
+                                    [--central]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -34,6 +35,13 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 distance and the distance to l's mirror image, and per chain (k, k) the distance to its own mirror
                 image; prints "modes: <n> sizes: ...".  --mode-threshold X (default 0.1, a default only: see
                 analysis.chain_modes): chains are linked when their distance is at most X of the largest possible
+  --central     with --select: the central sampled state of the chosen chains (analysis.central_from_records over
+                their chain_data.csv, mirrored chains oriented first): the saved record with the smallest sum of
+                Kendall distances to all the chosen chains' records, ties broken by the L1 distance of the taxon
+                limits -- one coherent order with its ranges.  Chains/central_order.csv: site, position;
+                Chains/central_taxa.csv: taxon, a, b; Chains/central_loss.csv: per chosen chain its flip, its best
+                row with that row's order loss and limit loss, the sum of the chain's order losses, and whether it
+                holds the central row; prints "central: chain <id> row <t>"
   --no-save     sample without writing files; prints one JSON summary per chain
   --rng         mt: GSL MT19937 as the reference (default); philox: the opt-in counter-based
                 Philox4x32-10 stream for sampling (statistically equivalent, not bit-equal)
@@ -139,6 +147,32 @@ def write_modes(ds, chains, root, threshold, device=0):
     return cm["size"].tolist()
 
 
+def write_central(ds, chains, root, device=0):
+    """Chains/central_order.csv, Chains/central_taxa.csv and Chains/central_loss.csv of the chosen chains: their
+    chain_data.csv rows, oriented against the first chain, and the row of smallest expected loss among them.  Returns
+    (chain id, row) of that row."""
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    flips = _oriented(ds, rec, device)
+    r = analysis.central_from_records(ds, rec, flips=flips, device=device)
+    ck, ct = r["central"]
+    with open(os.path.join(root, "Chains", "central_order.csv"), "w") as fh:
+        fh.write("site,position\n")
+        for n in range(ds.N):
+            fh.write("%d,%d\n" % (n, r["state"]["pi"][n]))
+    with open(os.path.join(root, "Chains", "central_taxa.csv"), "w") as fh:
+        fh.write("taxon,a,b\n")
+        for m in range(ds.M):
+            fh.write("%d,%d,%d\n" % (m, r["state"]["a"][m], r["state"]["b"][m]))
+    ol, ll = r["order_loss"].tolist(), r["limit_loss"].tolist()
+    with open(os.path.join(root, "Chains", "central_loss.csv"), "w") as fh:
+        fh.write("chain,flip,best_row,order_loss,limit_loss,order_loss_sum,is_central\n")
+        for k in range(len(chains)):
+            t = int(r["best"][k])
+            fh.write("%d,%d,%d,%d,%d,%d,%d\n" % (chains[k], flips[k], t, ol[k][t], ll[k][t], sum(ol[k]), k == ck))
+    return chains[ck], ct
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m seriation_amd", description=__doc__.split("\n\n")[0])
     ap.add_argument("dataset")
@@ -159,6 +193,7 @@ def main(argv=None):
     ap.add_argument("--waic", action="store_true")
     ap.add_argument("--modes", action="store_true")
     ap.add_argument("--mode-threshold", type=float, default=0.1)
+    ap.add_argument("--central", action="store_true")
     a = ap.parse_args(argv)
     if a.modes and a.no_save:
         ap.error("--modes needs the chain files: not with --no-save")
@@ -170,6 +205,8 @@ def main(argv=None):
         ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
     if a.relations and (a.select < 1 or a.no_save):
         ap.error("--relations needs --select K (and the chain files: not with --no-save)")
+    if a.central and (a.select < 1 or a.no_save):
+        ap.error("--central needs --select K (and the chain files: not with --no-save)")
     if a.chains < 1 or a.burnin < 0 or a.samples < 0 or a.thin < 1:
         ap.error("--chains and --thin must be >= 1, --burnin and --samples >= 0")
     devices = [int(d) for d in a.devices.split(",") if d.strip()]
@@ -209,6 +246,9 @@ def main(argv=None):
                 write_relations(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
             if a.waic:
                 write_waic(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, devices[0] if devices else 0)
+            if a.central:
+                print("central: chain %d row %d" % write_central(core.Dataset.load(a.dataset), chosen, a.root,
+                                                                  devices[0] if devices else 0))
     return 1 if any(s.get("consistent", 0) for s in summ) else 0
 
 

@@ -118,6 +118,16 @@ class sr_agree_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_central_out(ctypes.Structure):
+    _fields_ = [("flip", ctypes.POINTER(ctypes.c_uint8)),
+                ("order_loss", ctypes.POINTER(ctypes.c_int64)), ("limit_loss", ctypes.POINTER(ctypes.c_int64)),
+                ("pair_counts", ctypes.POINTER(ctypes.c_uint32)),
+                ("best", ctypes.POINTER(ctypes.c_int32)), ("state", ctypes.POINTER(ctypes.c_int32)),
+                ("central_chain", ctypes.c_int32), ("central_row", ctypes.c_int32),
+                ("scale", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 SINK_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                            ctypes.POINTER(sr_record))
 
@@ -136,6 +146,7 @@ PUBLIC_SYMBOLS = [
     "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals",
     "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce",
     "sr_agreement", "sr_session_agreement", "sr_agreement_distances", "sr_agreement_modes",
+    "sr_central", "sr_session_central", "sr_order_loss",
     "sr_strerror", "sr_device_count", "sr_version",
 ]
 
@@ -212,6 +223,10 @@ def _lib():
                                            P(ctypes.c_int64), P(c_double)]),
         "sr_agreement_modes": (c_int, [c_i32, P(ctypes.c_int64), P(ctypes.c_int64), ctypes.c_int64, c_double,
                                        P(c_i32), P(ctypes.c_uint8), P(c_i32), P(c_i32), P(c_i32)]),
+        "sr_central": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_central_out)]),
+        "sr_session_central": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_central_out)]),
+        "sr_order_loss": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, P(ctypes.c_uint8),
+                                  P(ctypes.c_uint32), c_i32, P(ctypes.c_int64), P(c_double)]),
         "sr_strerror": (ctypes.c_char_p, [c_int]),
         "sr_device_count": (c_int, []),
         "sr_version": (ctypes.c_char_p, []),

@@ -573,6 +573,92 @@ def chain_modes(dist, dist_mirror, scale, threshold=0.1):
     return {"mode": mode, "flip": flip, "medoid": medoid[:g].copy(), "size": size[:g].copy(), "n_modes": g}
 
 
+# ---------------------------------------------------------------- the central sampled state
+# One coherent answer: the saved record -- a real (pi, a, b) the sampler produced, a permutation that respects the hard
+# sites -- with the smallest posterior expected loss, the medoid of the draws (definitions: include/seriation.h).  The
+# order loss of a row is the sum of its Kendall distances to all the rows, ties broken by the L1 distance of the
+# limits.  Counts and losses come from the GPU (csrc/sr_central.hip); there is no CPU fallback.  Pool only the chains
+# of one mode, with that mode's flips.
+def _flip_arg(flips, n_sel):
+    if flips is None:
+        return None, None
+    f = np.ascontiguousarray(np.asarray(flips) != 0, dtype=np.uint8)
+    assert f.shape == (max(int(n_sel), 0),)
+    return f, f.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+
+
+def _central_outs(N, M, n_sel, count, flips, pair_counts):
+    n, c = max(int(n_sel), 0), max(int(count), 0)
+    arrs = {"order_loss": np.zeros((n, c), np.int64), "limit_loss": np.zeros((n, c), np.int64),
+            "best": np.zeros(n, np.int32)}
+    state = np.zeros(2 * M + N, np.int32)
+    out = L.sr_central_out()
+    f, fp = _flip_arg(flips, n_sel)
+    if f is not None:
+        out.flip = fp
+    out.order_loss = arrs["order_loss"].ctypes.data_as(_I64P)
+    out.limit_loss = arrs["limit_loss"].ctypes.data_as(_I64P)
+    out.best = arrs["best"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    out.state = state.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    if pair_counts:
+        arrs["pair_counts"] = np.zeros((N, N), np.uint32)
+        out.pair_counts = arrs["pair_counts"].ctypes.data_as(_U32P)
+    return out, arrs, state, [f]   # the last: the buffer the struct points into
+
+
+def _central_result(out, arrs, state, N, M):
+    arrs["central"] = (int(out.central_chain), int(out.central_row))
+    arrs["state"] = {"a": state[:M], "b": state[M:2 * M], "pi": state[2 * M:]}
+    arrs["scale"] = int(out.scale)
+    arrs["kernel_ms"] = out.kernel_ms
+    return arrs
+
+
+def central_from_records(dataset, ab_pi, flips=None, pair_counts=False, device=0):
+    """sr_central: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order) -> {"order_loss",
+    "limit_loss": int64 [n_sel][count], "best": int32 [n_sel] (each chain's row of smallest loss), "central": (chain,
+    row) of the smallest (order_loss, limit_loss, chain, row), "state": {"a": [M], "b": [M], "pi": [N]} int32 (that
+    row, reflected if its chain is flagged), "scale": T N (N - 1) / 2 (order_loss / scale is the expected normalised
+    Kendall distance to a draw), "kernel_ms"}; pair_counts=True adds "pair_counts" uint32 [N][N] (the pooled rows with
+    pi_i < pi_j).  flips [n_sel]: chains whose rows are reflected first."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    out, arrs, state, _keep = _central_outs(dataset.N, dataset.M, n_sel, count, flips, pair_counts)
+    _check(L.lib().sr_central(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n_sel,
+                              count, device, ctypes.byref(out)), "sr_central")
+    return _central_result(out, arrs, state, dataset.N, dataset.M)
+
+
+def central_from_session(session, chains, first=0, count=None, flips=None, pair_counts=False):
+    """sr_session_central: the same over a session's records still in HBM, rows [first, first + count) of chains
+    (session chain indices in selection order); "central" is (position in chains, row - first)."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs, state, _keep = _central_outs(session.ds.N, session.ds.M, len(chains), count, flips, pair_counts)
+    _check(L.lib().sr_session_central(session.h, ch, len(chains), first, count, ctypes.byref(out)),
+           "sr_session_central")
+    return _central_result(out, arrs, state, session.ds.N, session.ds.M)
+
+
+def order_loss(dataset, ab_pi, against, flips=None, device=0):
+    """sr_order_loss: the order loss alone, of the rows ab_pi [n_sel][count][2M+N] against counts the caller holds:
+    against uint32 [N][N] (any values, read as central's pair_counts; e.g. another mode's pooled counts, or
+    agreement's per-chain pair_counts summed) -> {"order_loss": int64 [n_sel][count], "kernel_ms"}."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    ag = np.ascontiguousarray(against, dtype=np.uint32)
+    assert ag.shape == (dataset.N, dataset.N)
+    loss = np.zeros((n_sel, count), np.int64)
+    _f, fp = _flip_arg(flips, n_sel)
+    ms = ctypes.c_double(0.0)
+    _check(L.lib().sr_order_loss(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n_sel,
+                                 count, fp, ag.ctypes.data_as(_U32P), device, loss.ctypes.data_as(_I64P),
+                                 ctypes.byref(ms)), "sr_order_loss")
+    return {"order_loss": loss, "kernel_ms": ms.value}
+
+
 def read_chain_cd(root, chains, taxa, manycd=False):
     """chain_data.csv of each chain -> the rates on the log scale, c = math.log(float(token)) of fields 3 and 4:
     float64 [n][lines][3] (the first c and d token and field 5, the line's loglik) or, manycd, [n][lines][2M] (all M
