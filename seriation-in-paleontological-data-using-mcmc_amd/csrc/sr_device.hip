@@ -187,16 +187,7 @@ __host__ __device__ static inline size_t sr_gm_ck(int N, int M, int TB) { return
 __host__ __device__ static inline size_t sr_gm_cbuf(int M) { return (size_t)2 * ((M + 63) / 64) * 64; }
 __host__ __device__ static inline size_t sr_sp_ck(int N, int TB) { return (size_t)((N >> 5) + 1) * 2 * TB; }   /* split chains */
 /* misc slots (8-byte words) */
-#define MS_TOT 0      /* 4 ints in 2 words */
-#define MS_DELTA 2
-#define MS_C 3
-#define MS_D 4
-#define MS_CC 5
-#define MS_DD 6
-#define MS_BLK 7
-#define MS_OFF 8
-#define MS_GEN 9
-#define MS_LOGL 10     /* (free: mcmc_logl is no longer broadcast) */
+#define MS_KREC 0     /* 7 words: the sweep's K record (slots 7-10 free) */
 #define MS_CAB 11
 #define MS_LLS 12
 #define MS_NEXACT 13
@@ -1788,6 +1779,87 @@ __device__ __forceinline__ void ptab_fill(uint32_t *ptab, const uint32_t *ring, 
   }
 }
 
+/* The record of proposal p of a phase-C batch lives in lane p of these five registers: vpk = i | j << 12 |
+ * inc1 << 24 | inc2 << 25 | veto << 26, vkr = Kn | r0 << 16 (pi3), the uniform_pos word, the words before it
+ * and the words to the proposal's end, both from the batch's cursor.  The two functions below are the fast
+ * forms of a batch's draws, shared by phase C and the sweep's pre-drawn first batch. */
+/* The sweep's swap from its fast-path table entry e (ptab[512 + delta], bit 25 set) into lane 0's record;
+ * base: the ring index of the batch's cursor. */
+__device__ __forceinline__ void prop_swap_fast(uint32_t e, const uint32_t *ring, uint32_t base, int lane, int &vpk,
+                                               int &vkr, int &vuw, int &vnd, int &voff, int &pend, int &off)
+{
+  const bool veto = (e >> 24) & 1u;
+  const int i = (int)(e & 4095u);
+  uint32_t iu = base + 3u;   /* the uniform_pos word (not drawn after a veto) */
+  iu = (iu >= SR_RING * SR_MT_N) ? iu - SR_RING * SR_MT_N : iu;
+  const uint32_t uw = veto ? 1u : sr_mt_temper(ring[iu]);
+  vpk = (lane == 0) ? (i | ((i + 1) << 12) | (int)(((e >> 26) & 3u) << 24) | (veto ? 1 << 26 : 0)) : vpk;
+  vkr = (lane == 0) ? 0 : vkr;
+  vuw = (lane == 0) ? (int)uw : vuw;
+  vnd = (lane == 0) ? (veto ? 1 : 3) : vnd;
+  voff = (lane == 0) ? (veto ? 1 : 4) : voff;
+  pend = 1;
+  off = veto ? 1 : 4;
+}
+
+/* The lane-parallel scan of a batch that starts at proposal p0, from the tables at index delta: proposals
+ * pend.. (pend, off: in / out) while each is on the fast path.  Two steps.  (1) the offset chain: proposal p
+ * starts where p-1 ended; a 5-bit entry per offset (lane l: offset l in bits 0-15, l + 64 in bits 16-31) holds,
+ * per kind, whether the fast path applies there and how many words it consumes (pi1 2 / 3, pi2 2 / 5, pi3 5),
+ * so each step is one readlane and a few scalar ops.  (2) lane p gathers its own proposal's record from the
+ * tables at its start offset. */
+__device__ __forceinline__ void prop_scan(const uint32_t *ptab, const uint32_t *ring, uint32_t base, int avail, int delta,
+                                          int p0, int lane, int &vpk, int &vkr, int &vuw, int &vnd, int &voff, int &pend,
+                                          int &off)
+{
+  uint32_t lent = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int t = delta + lane + 64 * h;   /* table index of batch offset lane + 64 h */
+    const int tc = min(t, 127);
+    const uint32_t a1 = ptab[tc], a2 = ptab[128 + tc], a3 = ptab[256 + tc];
+    const uint32_t e = ((a1 >> 25) & 1u) | ((((a1 >> 24) & 1u) ^ 1u) << 1) | (((a2 >> 25) & 1u) << 2) |
+                       (((a2 >> 24) & 1u) << 3) | (((a3 >> 25) & 1u) << 4);
+    lent |= (t < 128 ? e : 0u) << (16 * h);   /* past the tables: not ok (scalar path) */
+  }
+  const int sstart = pend;
+  int vstart = 0;
+#pragma unroll
+  for (int sI = 1; sI < 16; ++sI) {
+    if (sI < p0 || pend != sI || off + 5 > 128 || sI >= p0 + SR_BATCH_MAX) continue;
+    const int kind = prop_kind(sI);
+    const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)lent, off & 63) >> (16 * (off >> 6));
+    bool ok;
+    int adv;
+    if (kind == PK_PI1) { ok = e & 1u; adv = (e & 2u) ? 3 : 2; }
+    else if (kind == PK_PI2) { ok = (e >> 2) & 1u; adv = (e & 8u) ? 2 : 5; }
+    else { ok = (e >> 4) & 1u; adv = 5; }
+    if (!ok) continue;   /* rejection or zero word: scalar path */
+    vstart = (lane == sI) ? off : vstart;
+    off += adv;
+    pend = sI + 1;
+  }
+  {
+    const int o = vstart;
+    const int kind = prop_kind(lane & 15);
+    const int tc = min(delta + o, 127);
+    const uint32_t ra = ptab[(kind == PK_PI1 ? 0 : (kind == PK_PI2 ? 128 : 256)) + tc];
+    const uint32_t rb = (kind == PK_PI3) ? ptab[384 + tc] : 0u;
+    uint32_t iu = base + (uint32_t)min(o + (kind == PK_PI1 ? 2 : 4), avail - 1);   /* the uniform_pos word */
+    iu = (iu >= SR_RING * SR_MT_N) ? iu - SR_RING * SR_MT_N : iu;
+    const uint32_t ru = sr_mt_temper(ring[iu]);
+    const bool veto = (ra >> 24) & 1u;
+    const int nd = o + (kind == PK_PI1 ? 2 : (kind == PK_PI2 ? (veto ? 2 : 4) : 4));
+    if (lane >= sstart && lane < pend) {
+      vpk = (int)((ra & 0xffffffu) | (((ra >> 26) & 3u) << 24) | (veto ? 1u << 26 : 0u));
+      vkr = (int)((rb >> 16) | ((rb & 0xffffu) << 16));
+      vuw = (int)ru;
+      vnd = nd;
+      voff = nd + (veto ? 0 : 1);
+    }
+  }
+}
+
 /* Count changes of one taxon (limits a, b; position-ordered column Pm) under proposal q:
  * dt0 (zeros inside), dt1 (ones inside); the reference's df0 = -dt0 and df1 = -dt1 always
  * (mcmc.c:1175-1256 pi1, 1367-1436 pi2, 1568-1631 pi3).  hcnt/nhall: the wave's hard-site tables. */
@@ -2000,6 +2072,10 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
   static_assert(!LPRE || SP, "column prefixes in LDS beside HBM columns: split chains only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NWV = TB / 64;
+  /* the one-workgroup LDS-column kernels split their waves into two roles between the phase-A barrier and the
+     K barrier of each sweep: the first half draws c, d, one wave of the second half pre-draws
+     the sweep's first proposal batch */
+  constexpr bool ROLE = !GM && !MCD && !(SR_FN == 0 && TB == 512 && NWM == 17);   /* (generic 512 / 17: +48 B scratch) */
   /* wave: scalar in the HBM-column kernels (readfirstlane), so their per-wave LDS pointers live in SGPRs */
   const int tid = threadIdx.x, lane = tid & 63, wave = GM ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   /* SP: two workgroups per chain (sr_sp_half); both hold the whole block-uniform state (RNG ring,
@@ -2194,40 +2270,131 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
       if constexpr (!GM && !MCD) rng_topup<TB>(R, 0u, tid);
       SR_SYNC();
       FST(11);
-      {
-        int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+      CD K;
+      double vA, vB, rA, rB;
+      if constexpr (!ROLE) {
+        {
+          int s0 = 0, s1 = 0, s2 = 0, s3 = 0;
 #pragma unroll
-        for (int w = 0; w < NWV; ++w) {
-          const int *tw = tot + (par * NWV + w) * 4;
-          s0 += tw[0]; s1 += tw[1]; s2 += tw[2]; s3 += tw[3];
+          for (int w = 0; w < NWV; ++w) {
+            const int *tw = tot + (par * NWV + w) * 4;
+            s0 += tw[0]; s1 += tw[1]; s2 += tw[2]; s3 += tw[3];
+          }
+          if constexpr (SP) {   /* + the other half's totals */
+            int *xt = xb + par * 8;
+            if (tid == 0) { xst(xt + 4 * half, s0); xst(xt + 4 * half + 1, s1); xst(xt + 4 * half + 2, s2); xst(xt + 4 * half + 3, s3); }
+            xsync();
+            const int *yt = xt + 4 * (half ^ 1);
+            s0 += xld(yt); s1 += xld(yt + 1); s2 += xld(yt + 2); s3 += xld(yt + 3);
+          }
+          /* mcmc_samplec then mcmc_sampled: Beta(1 + f1, 1 + t0), Beta(1 + f0, 1 + t1) */
+          if constexpr (MCD) {
+            /* manycd: c_m for m = 0..M-1, then d_m, each a GSL beta of the taxon's own counts (mcmc.c:777-786,
+               807-816), in the reference's order from the one stream: every thread evaluates the same sequence
+               (block-wide ring refills), thread 0 stores; then each thread its taxa's log(1 - e^x) */
+            for (int k = 0; k < 2; ++k)
+              for (int m = 0; m < M; ++m) {
+                const double y = d_samplebeta<false>(R, cv[k * M + m], (double)(k ? scnt[M + m] : scnt[3 * M + m]),
+                                                     (double)(k ? scnt[2 * M + m] : scnt[m]), k ? SR_MIND : SR_MINC,
+                                                     k ? SR_MAXD : SR_MAXC, tid, TB, tb);
+                SR_SYNC();   /* every thread has read cv[k M + m] */
+                if (tid == 0) cv[k * M + m] = y;
+              }
+            SR_SYNC();
+            for (int m = tid; m < 2 * M; m += TB) cx[m] = sr_log_m(1. - sr_exp_m(cv[m], &tb), &tb);
+            SR_SYNC();
+            c = cv[0];
+            d = cv[M];
+            if (tid == 0) { misc[MS_ACC + 0] += M - 1; misc[MS_ACC + 1] += M - 1; }   /* samplec returns M (mcmc.c:785) */
+          } else if (!draw_cd_fast(R, c, d, s3, s0, s1, s2, tb, lane)) {
+            if (tid == 0) misc[MS_CDSEQ]++;
+            double cd2[2] = {c, d};
+            for (int k = 0; k < 2; ++k)
+              cd2[k] = d_samplebeta<false>(R, cd2[k], (double)(k ? s1 : s3), (double)(k ? s2 : s0), k ? SR_MIND : SR_MINC,
+                                           k ? SR_MAXD : SR_MAXC, tid, TB, tb);
+            c = cd2[0];
+            d = cd2[1];
+          }
+          FST(12);
+          if (tid == 0) { misc[MS_ACC + 0]++; misc[MS_ACC + 1]++; }
         }
-        if constexpr (SP) {   /* + the other half's totals */
-          int *xt = xb + par * 8;
-          if (tid == 0) { xst(xt + 4 * half, s0); xst(xt + 4 * half + 1, s1); xst(xt + 4 * half + 2, s2); xst(xt + 4 * half + 3, s3); }
-          xsync();
-          const int *yt = xt + 4 * (half ^ 1);
-          s0 += xld(yt); s1 += xld(yt + 1); s2 += xld(yt + 2); s3 += xld(yt + 3);
-        }
-        /* mcmc_samplec then mcmc_sampled: Beta(1 + f1, 1 + t0), Beta(1 + f0, 1 + t1) */
-        if constexpr (MCD) {
-          /* manycd: c_m for m = 0..M-1, then d_m, each a GSL beta of the taxon's own counts (mcmc.c:777-786,
-             807-816), in the reference's order from the one stream: every thread evaluates the same sequence
-             (block-wide ring refills), thread 0 stores; then each thread its taxa's log(1 - e^x) */
-          for (int k = 0; k < 2; ++k)
-            for (int m = 0; m < M; ++m) {
-              const double y = d_samplebeta<false>(R, cv[k * M + m], (double)(k ? scnt[M + m] : scnt[3 * M + m]),
-                                                   (double)(k ? scnt[2 * M + m] : scnt[m]), k ? SR_MIND : SR_MINC,
-                                                   k ? SR_MAXD : SR_MAXC, tid, TB, tb);
-              SR_SYNC();   /* every thread has read cv[k M + m] */
-              if (tid == 0) cv[k * M + m] = y;
+        /* cc = log(1 - e^c) on even lanes, dd = log(1 - e^d) on odd lanes: one evaluation chain
+           instead of two */
+        const bool oddl = (lane & 1) != 0;
+        const double l1 = sr_log_m(1. - sr_exp_m(oddl ? d : c, &tb), &tb);
+        K.c = c; K.d = d; K.cc = readlane_f64(l1, 0); K.dd = readlane_f64(l1, 1); K.ec = ec;
+        /* one position's value in q (log2 units): zero -> d - cc, one -> dd - c */
+        vA = (K.d - K.cc) * 1.4426950408889634;
+        vB = (K.dd - K.c) * 1.4426950408889634;
+        const double r2 = sr_exp_m(oddl ? K.c - K.dd : K.cc - K.d, &tb);
+        rA = readlane_f64(r2, 0); rB = readlane_f64(r2, 1);   /* 2^-vA, 2^-vB */
+      } else {
+        /* Role split.  The c, d draws are a chain of dependent f64 VALU operations on a few
+           lanes, the draw of the sweep's first proposal batch a chain of scalar ALU, readlane and LDS round trips,
+           and neither needs the other: the batch's inputs are the ring and the proposal tables filled above.  Waves
+           [0, NWV / 2) run the totals and the c, d draws and publish them in the K record; wave NWV / 2 meanwhile
+           draws the batch at (tblk, toff) into LDS; the K barrier joins them.  A SIMD then holds one chain of each
+           sort where two copies of each took turns. */
+        const bool drawer = __builtin_amdgcn_readfirstlane(tid) >= TB / 2;
+        double *krec = (double *)&misc[MS_KREC];   /* {fast path ok, c, d, cc, dd, rA, rB} */
+        bool cdok = true;
+        K.cc = 0.0; K.dd = 0.0; rA = 0.0; rB = 0.0;
+        /* cc, dd and the step ratios as above */
+        auto cd_derive = [&]() {
+          const bool oddl = (lane & 1) != 0;
+          const double l1 = sr_log_m(1. - sr_exp_m(oddl ? d : c, &tb), &tb);
+          K.cc = readlane_f64(l1, 0); K.dd = readlane_f64(l1, 1);
+          const double r2 = sr_exp_m(oddl ? c - K.dd : K.cc - d, &tb);
+          rA = readlane_f64(r2, 0); rB = readlane_f64(r2, 1);
+        };
+        auto totals = [&](int &s0, int &s1, int &s2, int &s3) {
+          s0 = s1 = s2 = s3 = 0;
+#pragma unroll
+          for (int w = 0; w < NWV; ++w) {
+            const int *tw = tot + (par * NWV + w) * 4;
+            s0 += tw[0]; s1 += tw[1]; s2 += tw[2]; s3 += tw[3];
+          }
+        };
+        if (!drawer) {
+          int s0, s1, s2, s3;
+          totals(s0, s1, s2, s3);
+          cdok = draw_cd_fast(R, c, d, s3, s0, s1, s2, tb, lane);
+          FST(12);
+          if (cdok) cd_derive();
+          if (tid == 0) {
+            misc[MS_ACC + 0]++; misc[MS_ACC + 1]++;
+            krec[0] = cdok ? 1.0 : 0.0;
+            krec[1] = c; krec[2] = d; krec[3] = K.cc; krec[4] = K.dd; krec[5] = rA; krec[6] = rB;
+          }
+        } else if (__builtin_amdgcn_readfirstlane(tid) < TB / 2 + 64) {
+          /* the first batch as phase C draws it when it starts at (tblk, toff): the swap from its table entry, the
+             scan from table index 0.  Only the fast forms: where phase C would leave them the batch ends there, or
+             there is none (a swap entry off the fast path), and phase C draws in place as before.  The cursor R is
+             not touched.  The record: [0] the batch's pend (0: none), [4 + 4 p ..] lane p's words, in the count
+             sums' other parity -- last written by the previous sweep's last batch, next by this sweep's second. */
+          int qpk = 1 << 26, qkr = 0, quw = 1, qnd = 0, qoff = 0, qpend = 0, qo = 0;
+          if (tvalid) {
+            const uint32_t qblk = __builtin_amdgcn_readfirstlane(tblk), qof = __builtin_amdgcn_readfirstlane(toff);
+            const uint32_t qbase = (qblk & (SR_RING - 1)) * SR_MT_N + qof;
+            const int qavail = min((int)((__builtin_amdgcn_readfirstlane(R.gen) - qblk) * SR_MT_N - qof), 128);
+            const uint32_t e = ptab[512];
+            if ((e >> 25) & 1u) {
+              prop_swap_fast(e, ring, qbase, lane, qpk, qkr, quw, qnd, qoff, qpend, qo);
+              prop_scan(ptab, ring, qbase, qavail, 0, 0, lane, qpk, qkr, quw, qnd, qoff, qpend, qo);
             }
-          SR_SYNC();
-          for (int m = tid; m < 2 * M; m += TB) cx[m] = sr_log_m(1. - sr_exp_m(cv[m], &tb), &tb);
-          SR_SYNC();
-          c = cv[0];
-          d = cv[M];
-          if (tid == 0) { misc[MS_ACC + 0] += M - 1; misc[MS_ACC + 1] += M - 1; }   /* samplec returns M (mcmc.c:785) */
-        } else if (!draw_cd_fast(R, c, d, s3, s0, s1, s2, tb, lane)) {
+          }
+          int *prec = part + ((bpar ^ 1) * 16) * NWV * 8;
+          if (lane < 16) *reinterpret_cast<int4 *>(prec + 4 + 4 * lane) = make_int4(qpk, qkr, quw, qnd | (qoff << 16));
+          if (lane == 0) prec[0] = qpend;
+        }
+        SR_SYNC();   /* the K barrier: the K record and the pre-drawn batch are published */
+        cdok = __builtin_amdgcn_readfirstlane((int)(krec[0] != 0.0)) != 0;
+        if (!cdok) {
+          /* the sequential GSL draws (block-wide ring refills inside): every wave together, from the sweep's cursor,
+             as before.  Phase C then starts elsewhere than (tblk, toff) and leaves the pre-drawn batch alone -- or at
+             that very cursor, where the batch is what it would draw from the same tables. */
+          int s0, s1, s2, s3;
+          totals(s0, s1, s2, s3);
           if (tid == 0) misc[MS_CDSEQ]++;
           double cd2[2] = {c, d};
           for (int k = 0; k < 2; ++k)
@@ -2235,21 +2402,17 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                                          k ? SR_MAXD : SR_MAXC, tid, TB, tb);
           c = cd2[0];
           d = cd2[1];
+          cd_derive();
+        } else if (drawer) {
+          c = readlane_f64(krec[1], 0); d = readlane_f64(krec[2], 0);
+          K.cc = readlane_f64(krec[3], 0); K.dd = readlane_f64(krec[4], 0);
+          rA = readlane_f64(krec[5], 0); rB = readlane_f64(krec[6], 0);
+          rng_skip(R, 8);
         }
-        FST(12);
-        if (tid == 0) { misc[MS_ACC + 0]++; misc[MS_ACC + 1]++; }
+        K.c = c; K.d = d; K.ec = ec;
+        vA = (K.d - K.cc) * 1.4426950408889634;
+        vB = (K.dd - K.c) * 1.4426950408889634;
       }
-      CD K;
-      /* cc = log(1 - e^c) on even lanes, dd = log(1 - e^d) on odd lanes: one evaluation chain
-         instead of two */
-      const bool oddl = (lane & 1) != 0;
-      const double l1 = sr_log_m(1. - sr_exp_m(oddl ? d : c, &tb), &tb);
-      K.c = c; K.d = d; K.cc = readlane_f64(l1, 0); K.dd = readlane_f64(l1, 1); K.ec = ec;
-      /* one position's value in q (log2 units): zero -> d - cc, one -> dd - c */
-      const double vA = (K.d - K.cc) * 1.4426950408889634;
-      const double vB = (K.dd - K.c) * 1.4426950408889634;
-      const double r2 = sr_exp_m(oddl ? K.c - K.dd : K.cc - K.d, &tb);
-      const double rA = readlane_f64(r2, 0), rB = readlane_f64(r2, 1);   /* 2^-vA, 2^-vB */
       if ((!GM || wave == NWV - 1) && lane < 16) {   /* per-wave (GM: shared) tables for 4 walk entries with bits = lane */
         double sc[5];
         const double pr = t4_row(lane, rA, rB, sc);
@@ -2526,31 +2689,40 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
               pend = p + 1;
               return true;
           };
+          /* the sweep's pre-drawn first batch, when phase C starts where it was drawn (the c, d draws took their
+             8 words): lane p's record in one LDS round trip */
+          bool predrawn = false;
+          if constexpr (ROLE) {
+            if (p0 == 0) {
+              const int *prec = part + ((bpar ^ 1) * 16) * NWV * 8;
+              const int rp = (tvalid && rblk == tblk && roff == toff) ? __builtin_amdgcn_readfirstlane(prec[0]) : 0;
+              if (rp > 0) {
+                if (lane < 16) {
+                  const int4 q = *reinterpret_cast<const int4 *>(prec + 4 + 4 * lane);
+                  vpk = q.x; vkr = q.y; vuw = q.z; vnd = q.w & 0xffff; voff = q.w >> 16;
+                }
+                pend = rp;
+                predrawn = true;
+              }
+#if defined(SR_STAMPS) && !defined(SR_STAMP_FINE)
+              if (tid == 0) misc[predrawn ? 45 : 46] += 1;   /* pre-drawn first batches used / discarded */
+#endif
+            }
+          }
           /* the swap (accepted ~44 %) is drawn first and forms its own batch: from the sweep's table when
              phase C starts inside it and the entry is on the fast path, else by the scalar path */
-          if (p0 == 0) {
+          if (p0 == 0 && !(ROLE && predrawn)) {
             const int dlt = tvalid ? (int)((rblk - tblk) * SR_MT_N + roff) - (int)toff : -1;
             const uint32_t e = (dlt >= 0 && dlt < 128) ? ptab[512 + dlt] : 0u;
             if ((e >> 25) & 1u) {
-              const bool veto = (e >> 24) & 1u;
-              const int i = (int)(e & 4095u);
-              uint32_t iu = base + 3u;   /* the uniform_pos word (not drawn after a veto) */
-              iu = (iu >= SR_RING * SR_MT_N) ? iu - SR_RING * SR_MT_N : iu;
-              const uint32_t uw = veto ? 1u : sr_mt_temper(ring[iu]);
-              vpk = (lane == 0) ? (i | ((i + 1) << 12) | (int)(((e >> 26) & 3u) << 24) | (veto ? 1 << 26 : 0)) : vpk;
-              vkr = (lane == 0) ? 0 : vkr;
-              vuw = (lane == 0) ? (int)uw : vuw;
-              vnd = (lane == 0) ? (veto ? 1 : 3) : vnd;
-              voff = (lane == 0) ? (veto ? 1 : 4) : voff;
-              pend = 1;
-              off = veto ? 1 : 4;
+              prop_swap_fast(e, ring, base, lane, vpk, vkr, vuw, vnd, voff, pend, off);
             } else {
               (void)scalar_one(0);
             }
           }
           /* a fast-path swap is drawn into one batch with proposals 1..15 (its acceptance, ~44 %, then wastes their
              terms; not in the HBM-column kernels, whose proposal terms cost far more) */
-          if (p0 > 0 || (!GM && pend == 1)) {
+          if ((p0 > 0 || (!GM && pend == 1)) && !(ROLE && predrawn)) {
             /* Lane-parallel draws: lane l evaluates "a pi1 / pi2 / pi3 proposal starting at word
                offset o" for o = l and o = l + 64 (words o..o+4) into ptab; the scan below then walks
                the batch's actual offsets reading those results.  ok = no GSL rejection and a nonzero
@@ -2570,57 +2742,8 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
               wsync();
             }
             FST(15);
-            /* scan, two steps.  (1) the offset chain: proposal p starts where p-1 ended; a 5-bit
-               entry per offset (lane l: offset l in bits 0-15, l + 64 in bits 16-31) holds, per kind,
-               whether the fast path applies there and how many words it consumes (pi1 2 / 3,
-               pi2 2 / 5, pi3 5), so each step is one readlane and a few scalar ops.  (2) lane p
-               gathers its own proposal's record from the tables at its start offset. */
-            uint32_t lent = 0;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const int t = delta + lane + 64 * h;   /* table index of batch offset lane + 64 h */
-              const int tc = min(t, 127);
-              const uint32_t a1 = ptab[tc], a2 = ptab[128 + tc], a3 = ptab[256 + tc];
-              const uint32_t e = ((a1 >> 25) & 1u) | ((((a1 >> 24) & 1u) ^ 1u) << 1) | (((a2 >> 25) & 1u) << 2) |
-                                 (((a2 >> 24) & 1u) << 3) | (((a3 >> 25) & 1u) << 4);
-              lent |= (t < 128 ? e : 0u) << (16 * h);   /* past the tables: not ok (scalar path) */
-            }
-            const int sstart = pend;
-            int vstart = 0;
-#pragma unroll
-            for (int sI = 1; sI < 16; ++sI) {
-              if (sI < p0 || pend != sI || off + 5 > 128 || sI >= p0 + SR_BATCH_MAX) continue;
-              const int kind = prop_kind(sI);
-              const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)lent, off & 63) >> (16 * (off >> 6));
-              bool ok;
-              int adv;
-              if (kind == PK_PI1) { ok = e & 1u; adv = (e & 2u) ? 3 : 2; }
-              else if (kind == PK_PI2) { ok = (e >> 2) & 1u; adv = (e & 8u) ? 2 : 5; }
-              else { ok = (e >> 4) & 1u; adv = 5; }
-              if (!ok) continue;   /* rejection or zero word: scalar path */
-              vstart = (lane == sI) ? off : vstart;
-              off += adv;
-              pend = sI + 1;
-            }
-            {
-              const int o = vstart;
-              const int kind = prop_kind(lane & 15);
-              const int tc = min(delta + o, 127);
-              const uint32_t ra = ptab[(kind == PK_PI1 ? 0 : (kind == PK_PI2 ? 128 : 256)) + tc];
-              const uint32_t rb = (kind == PK_PI3) ? ptab[384 + tc] : 0u;
-              uint32_t iu = base + (uint32_t)min(o + (kind == PK_PI1 ? 2 : 4), avail - 1);   /* the uniform_pos word */
-              iu = (iu >= SR_RING * SR_MT_N) ? iu - SR_RING * SR_MT_N : iu;
-              const uint32_t ru = sr_mt_temper(ring[iu]);
-              const bool veto = (ra >> 24) & 1u;
-              const int nd = o + (kind == PK_PI1 ? 2 : (kind == PK_PI2 ? (veto ? 2 : 4) : 4));
-              if (lane >= sstart && lane < pend) {
-                vpk = (int)((ra & 0xffffffu) | (((ra >> 26) & 3u) << 24) | (veto ? 1u << 26 : 0u));
-                vkr = (int)((rb >> 16) | ((rb & 0xffffu) << 16));
-                vuw = (int)ru;
-                vnd = nd;
-                voff = nd + (veto ? 0 : 1);
-              }
-            }
+            /* the scan: the batch's offset chain, then lane p's gather of its own record */
+            prop_scan(ptab, ring, base, avail, delta, p0, lane, vpk, vkr, vuw, vnd, voff, pend, off);
           }
           for (int p = pend; p < 16; ++p) {   /* scalar path: the batch's first proposal after a fast-path stop */
             if (p0 == 0 && p == 1) break;     /* the swap batch (merged: the lane-parallel scan's proposals follow) */
@@ -3149,6 +3272,7 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
                   for (int q_ = 0; q_ < 3; ++q_) A.dbg[blockIdx.x * 17 * 8 + 5 + q_] += misc[40 + q_];
 #if !defined(SR_STAMP_FINE) && !defined(SR_STAMP_GIBBS)
                   if (TB <= 512) A.dbg[(blockIdx.x * 17 + 9) * 8 + 0] += misc[43];   /* (row 9: no wave's stamps) */
+                  if (TB <= 512) for (int q_ = 0; q_ < 2; ++q_) A.dbg[(blockIdx.x * 17 + 9) * 8 + 1 + q_] += misc[45 + q_];
 #endif
 #if defined(SR_STAMP_GIBBS) || defined(SR_STAMP_FINE)
                   for (int q_ = 0; q_ < 3; ++q_) A.dbg[blockIdx.x * 17 * 8 + 5 + q_] = misc[MS_FBK + 26 + q_];
@@ -3158,19 +3282,24 @@ __global__ __launch_bounds__(TB) void sr_sweep_kernel(KArgs A)
 #endif
   __syncthreads();
   const KArgs &B = kargs_late(A);
+  /* the role-split kernels: the state stores' addresses from an opaque copy of the thread index, or they are
+     computed above the sweep loop beside the state load's and kept through it (10-12 VGPRs in the bench kernel,
+     spilled).  Not in the generic 256- and 512-thread kernels, which spill more with it. */
+  int tid_st = tid;
+  if constexpr (ROLE && (SR_FN > 0 || TB == 1024)) __asm__ volatile("" : "+v"(tid_st));
   uint32_t *oP = B.P + (size_t)chain * NW * M;
-  if (!GM) for (int i = tid; i < NW * M; i += TB) oP[i] = P[i];
+  if (!GM) for (int i = tid_st; i < NW * M; i += TB) oP[i] = P[i];
   const int32_t *rc = rcur ? rpiB : rpiA;
   int32_t *orpi = B.rpi + (size_t)chain * N;
   uint32_t *omt = B.mt + (size_t)chain * SR_RING * SR_MT_N;
   if (!SP || half == 0) {   /* SP: block-uniform state, identical in both halves */
-    for (int i = tid; i < N; i += TB) orpi[i] = rc[i];
-    for (int i = tid; i < SR_RING * SR_MT_N; i += TB) omt[i] = ring[i];
+    for (int i = tid_st; i < N; i += TB) orpi[i] = rc[i];
+    for (int i = tid_st; i < SR_RING * SR_MT_N; i += TB) omt[i] = ring[i];
   }
   int32_t *oab = B.ab + (size_t)chain * 2 * M;
-  if (!GM) for (int i = tid; i < 2 * M; i += TB) oab[i] = sab[i];
+  if (!GM) for (int i = tid_st; i < 2 * M; i += TB) oab[i] = sab[i];
   int32_t *ocnt = B.cnt + (size_t)chain * 4 * M;
-  if (!GM) for (int i = tid; i < 4 * M; i += TB) ocnt[i] = scnt[i];
+  if (!GM) for (int i = tid_st; i < 4 * M; i += TB) ocnt[i] = scnt[i];
   if (tid == 0) {
     uint64_t *acc = B.acc + (size_t)chain * SR_NACC;
     if (!SP || half == 0) {

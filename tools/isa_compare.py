@@ -6,7 +6,8 @@ source text, replaced by a fixed one) and the .amdhsa_ / resource figures of its
 (VGPRs, SGPRs, spills, scratch, LDS, code bytes).  Prints one row per function: equal or the figures side by side.
 Before hashing, a line loses its `;` comment and trailing blanks, runs of blanks become one, and the function's index
 within the unit goes from the local labels (.LBB<k>_, BB<k>_, .Ltmp<k>, .Lfunc_begin<k>, .Lfunc_end<k>): a function
-added or removed earlier in the unit shifts that index in every function after it.
+added or removed earlier in the unit shifts that index in every function after it.  So does the unit-wide count in
+the long branches' .Lpost_getpc<k> labels when an earlier function gains or loses one.
 --rename-old applies re.sub(REGEX, REPL) to OLD's text (write REGEX to match symbol names only), for a kernel whose
 template parameters changed: its label, and its name in the kernel descriptor and section lines of its body."""
 import argparse
@@ -15,7 +16,7 @@ import re
 import subprocess
 
 KEYS = ("NumVgprs", "NumAgprs", "NumSgprs", "ScratchSize", "Occupancy", "codeLenInByte", "LDSByteSize")
-LOCAL = re.compile(r"(\.LBB|\bBB|\.Ltmp|\.Lfunc_begin|\.Lfunc_end)\d+")
+LOCAL = re.compile(r"(\.LBB|\bBB|\.Ltmp|\.Lfunc_begin|\.Lfunc_end|\.Lpost_getpc)\d+")
 
 
 def demangle(names):

@@ -64,6 +64,8 @@ if not os.environ.get("SR_FINE") and not os.environ.get("SR_GIBBS_STATS"):
     bs = np.concatenate([out[:, 9, 0:1], out[:, 0, 5:8]], axis=1).astype(np.float64).mean(0) / 2 / sweeps   # coarse builds
     print("  phase-C batches/sweep %.3f; proposals drawn into batches/sweep %.2f (16 needed); proposal-table refills/sweep "
           "%.3f; scalar-path proposals/sweep %.3f" % (bs[1], bs[2], bs[3], bs[0]))
+    pd = out[:, 9, 1:3].astype(np.float64).mean(0) / 2 / sweeps   # the role-split kernels' pre-drawn first batches
+    print("  pre-drawn first batches/sweep: used %.3f, discarded %.3f" % (pd[0], pd[1]))
 print("  accepted per sweep (profiled launch, chain mean): pi1 %.3f pi2 %.3f swap %.3f pi3 %.3f" % tuple(acc[3:7]))
 if os.environ.get("SR_BAR") and nw <= 8:   # SR_STAMPS + SR_STAMP_BAR builds: cycles inside the sweep loop's barriers
     bar = out[:, 9:9 + nw, 7].astype(np.float64) / 2.0 / sweeps
