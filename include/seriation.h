@@ -413,6 +413,68 @@ int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t
 /* the reduction alone, on the host: scalars, site_elpd and taxon_elpd of out from lppd, pwaic [N][M] */
 int sr_waic_reduce(int32_t N, int32_t M, const double *lppd, const double *pwaic, sr_waic_out *out);
 
+/* ---- Posterior predictive checks over saved samples: exact integers, the replicates defined to the bit ----
+ * (an extension: WAIC ranks the two rate models against each other; whether the preferred one is adequate -- one
+ * false-zero rate for every taxon, no per-site sampling effort -- is a posterior predictive check on realised
+ * discrepancies, Gelman, Meng & Stern 1996.)  For every saved sample and every replicate a 0/1 matrix is drawn from
+ * the model at the sample's (pi, a, b, c, d); a discrepancy of the replicate is compared with the same discrepancy of
+ * X under the same sample, and the comparisons are tallied.
+ * Inputs: records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position, chains in selection order;
+ * sample (k, r), row r of chain k, has index t = k * count + r, T = n_sel * count.  The rates are exactly as sr_waic
+ * takes them: manycd = 0: cd [n_sel][count][3], (c, d, loglik) rows, loglik not read; manycd != 0: cd
+ * [n_sel][count][2M], c[M] then d[M].  seed is any uint64 (0 is a seed like any other); reps, 1..64, the number of
+ * replicates per sample.  No flip input: reflecting a chain (a' = N - b, b' = N - a, pi' = N - 1 - pi) changes no
+ * alive bit, no span and -- the counter holds the site, not the position -- no random word.
+ * The replicate matrix: ec = exp(c), ed = exp(d) (this library's exp, bit for bit the C library's);
+ *   thr_alive = (uint64)((1.0 - ed) * 4294967296.0), thr_dead = (uint64)(ec * 4294967296.0): both scalings are exact,
+ *   both conversions truncate, the values reach 0 and 2^32, so they are compared in 64 bits;
+ *   cell (n, m) is alive when a_m <= pi_n < b_m, compared in int32 (any int16 is legal);
+ *   w = philox4x32_10(ctr = {n, m >> 2, t, rep}, key = {seed lo, seed hi ^ 0x50504331})[m & 3]: one call serves one
+ *   site and four consecutive taxa; the key constant keeps these streams apart from a Philox-mode sampler's;
+ *   x_rep = w < (alive ? thr_alive : thr_dead).
+ * Discrepancies of a 0/1 matrix Y under sample t, int32, per taxon m, in this index order:
+ *   0 ones   the sites with y = 1
+ *   1 span   0 if ones = 0, else max pi_n - min pi_n + 1 over the sites with y = 1 (pi need not be a permutation)
+ *   2 gaps   span - ones: the zeros between the first and the last occurrence
+ *   3 f0     the sites alive with y = 0
+ *   4 f1     the sites not alive with y = 1
+ * per site n: rich, the sum of y[n][m] over m (for Y = X the row sum, the same under every sample); in total: each of
+ * the five taxon statistics summed over m, int64.
+ * Outputs, over the pairs = T * reps (sample, replicate) pairs; every pointer is optional (NULL = skip), the scalars
+ * are always written:
+ *   taxon_gt, taxon_eq [5][M] uint32        the pairs with rep > obs, with rep == obs
+ *   taxon_sum_obs, taxon_sum_rep [5][M] int64  the sums over the same pairs (each sample's observed value counts
+ *                                           reps times)
+ *   site_gt, site_eq [N] uint32, site_sum_rep [N] int64   the same for rich
+ *   total_obs [n_sel][count][5], total_rep [n_sel][count][reps][5] int64   the totals of every sample and replicate
+ *   total_gt[5], total_eq[5]                the tallies of the totals; pairs; kernel_ms, the kernels' time
+ * A posterior predictive p-value is (gt + 0.5 * eq) / pairs.
+ * SR_EINVAL: NULL ds, ab_pi, cd or out, n_sel <= 0, count < 1, reps outside 1..64, T * reps >= 2^31, N outside
+ * 1..32767, M < 1, any c or d that is read outside [-700, -2^-50] or NaN; the session form also for rows beyond the
+ * buffered records or a chain index out of range.  SR_EUNSUPPORTED: N M > 2^27, or a library built without the device
+ * layer.  All reported before any kernel runs, the outputs untouched.  Device scratch is bounded: the samples are
+ * taken in batches of at most SR_PPC_SCRATCH bytes (environment, default 256 MiB) of row sums, totals and
+ * thresholds; the results do not depend on it. */
+typedef struct {
+  uint32_t *taxon_gt, *taxon_eq;            /* out: [5][M], NULL = skip */
+  int64_t *taxon_sum_obs, *taxon_sum_rep;   /* out: [5][M], NULL = skip */
+  uint32_t *site_gt, *site_eq;              /* out: [N], NULL = skip */
+  int64_t *site_sum_rep;                    /* out: [N], NULL = skip */
+  int64_t *total_obs;                       /* out: [n_sel][count][5], NULL = skip */
+  int64_t *total_rep;                       /* out: [n_sel][count][reps][5], NULL = skip */
+  int64_t total_gt[5], total_eq[5];
+  int64_t pairs;
+  double kernel_ms;
+} sr_ppc_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M and X */
+int sr_ppc(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel, int32_t count,
+           uint64_t seed, int32_t reps, int32_t device, sr_ppc_out *out);
+/* the session's own records and rates in HBM, rows [first, first+count) of chains[] (selection order), on the
+   session's stream; manycd is the session's; the session's state and records are left untouched */
+int sr_session_ppc(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count, uint64_t seed,
+                   int32_t reps, sr_ppc_out *out);
+
 /* ---- chain agreement: pairwise order distances between chains and mode clustering: exact integers ----
  * (an extension: the reference's choose_chains ranks chains by mean -loglik and never asks whether they sampled the
  * same order.)  Records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position; only the pi part is

@@ -1051,7 +1051,7 @@ static double *post_slot(sr_posterior_out *o, int k)
 
 /* ---- the record view of the analyses below (sr_records.h) ---- */
 /* The view's functions (sr_records.hip) and the analyses' entry points (sr_post, sr_diag, sr_marg, sr_rel, sr_agree,
-   sr_waic, sr_central .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
+   sr_waic, sr_central, sr_ppc .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
    every analysis reports SR_EUNSUPPORTED, after its argument checks and before anything is uploaded. */
 #define SR_WEAK(f) extern __typeof__(f) f __attribute__((weak))
 SR_WEAK(sr_recview_host);
@@ -1066,6 +1066,7 @@ SR_WEAK(sra_distances_host);
 SR_WEAK(srw_waic);
 SR_WEAK(src_central);
 SR_WEAK(src_order_loss);
+SR_WEAK(srq_ppc);
 
 /* the device layer's return code (0, -1, -4, anything else) as an SR_* code */
 static int sr_code_of(int rc) { return rc == 0 ? SR_OK : (rc == -1 ? SR_EINVAL : (rc == -4 ? SR_ENOMEM : SR_EDEVICE)); }
@@ -1800,6 +1801,83 @@ SR_API int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, 
     if (!rc && !waic_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
   }
   if (!rc) rc = waic_run(&v, &s->ds, out, rows, cdw, manycd);
+  sr_recview_release(&v);
+  free(rows);
+  free(buf);
+  return rc;
+}
+
+/* ---- posterior predictive checks (definitions: include/seriation.h) ---- */
+/* the argument checks both forms share, made before any device call */
+static int ppc_check(const sr_ppc_out *out, int32_t n_sel, int32_t count, int32_t reps, int32_t N, int32_t M)
+{
+  if (!out || n_sel <= 0 || count < 1 || reps < 1 || reps > 64) return SR_EINVAL;
+  if ((int64_t)n_sel * count * reps >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  return SR_OK;
+}
+
+static int ppc_run(const sr_recview *v, const sr_dataset *ds, sr_ppc_out *out, const double *const *cd, int cdw,
+                   int manycd, uint64_t seed, int reps)
+{
+  long long gt[5], eq[5];
+  float ms = 0.0f;
+  const int rc = sr_code_of(srq_ppc(v, ds->N, ds->M, ds->X, cd, cdw, manycd, seed, reps, out->taxon_gt, out->taxon_eq,
+                                    (long long *)out->taxon_sum_obs, (long long *)out->taxon_sum_rep, out->site_gt,
+                                    out->site_eq, (long long *)out->site_sum_rep, (long long *)out->total_obs,
+                                    (long long *)out->total_rep, gt, eq, &ms));
+  if (rc) return rc;
+  for (int i = 0; i < 5; i++) { out->total_gt[i] = gt[i]; out->total_eq[i] = eq[i]; }
+  out->pairs = (int64_t)v->n_sel * v->count * reps;
+  out->kernel_ms = ms;
+  return SR_OK;
+}
+
+SR_API int sr_ppc(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel,
+                  int32_t count, uint64_t seed, int32_t reps, int32_t device, sr_ppc_out *out)
+{
+  if (!ds || !ab_pi || !cd) return SR_EINVAL;
+  int rc = ppc_check(out, n_sel, count, reps, ds->N, ds->M);
+  if (rc) return rc;
+  if (!ds->X) return SR_EINVAL;
+  const int Mt = manycd ? ds->M : 1, cdw = manycd ? 2 * ds->M : 3;
+  if (!waic_cd_ok(cd, (int32_t)((int64_t)n_sel * count), cdw, Mt)) return SR_EINVAL;
+  if ((int64_t)ds->N * ds->M > WAIC_CELLS_MAX) return SR_EUNSUPPORTED;
+  if (!srq_ppc) return SR_EUNSUPPORTED;
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  if (!rows) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) rows[k] = cd + (size_t)k * count * cdw;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = ppc_run(&v, ds, out, rows, cdw, manycd != 0, seed, reps);
+  sr_recview_release(&v);
+  free(rows);
+  return rc;
+}
+
+SR_API int sr_session_ppc(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                          uint64_t seed, int32_t reps, sr_ppc_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = ppc_check(out, n_sel, count, reps, s->ds.N, s->ds.M);
+  if (rc) return rc;
+  sr_recview v;
+  rc = session_view(s, chains, n_sel, first, count,
+                    (int64_t)s->ds.N * s->ds.M > WAIC_CELLS_MAX || !srq_ppc ? SR_EUNSUPPORTED : SR_OK, &v);
+  if (rc) return rc;
+  const int M = s->ds.M, manycd = s->opts.manycd != 0;
+  const int Mt = manycd ? M : 1, cdw = manycd ? 2 * M : 3;
+  /* the rates come to the host as sr_session_waic fetches them */
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  double *buf = (double *)malloc(sizeof(double) * (size_t)(manycd ? s->nchains : n_sel) * count * cdw);
+  rc = (rows && buf) ? SR_OK : SR_ENOMEM;
+  if (!rc && manycd && srk_fetch_cdv(s->dev, first, count, buf)) rc = SR_EDEVICE;
+  for (int k = 0; k < n_sel && !rc; k++) {
+    rows[k] = buf + (size_t)(manycd ? chains[k] : k) * count * cdw;
+    if (!manycd && srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, (double *)rows[k])) rc = SR_EDEVICE;
+    if (!rc && !waic_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
+  }
+  if (!rc) rc = ppc_run(&v, &s->ds, out, rows, cdw, manycd, seed, reps);
   sr_recview_release(&v);
   free(rows);
   free(buf);

@@ -1,6 +1,7 @@
 /*
  * sr_records.h -- the record view: how the analyses over saved records (posterior summaries, convergence
- * diagnostics, marginals, taxon-pair relations, WAIC, chain agreement, the central state) address the rows they read, and those
+ * diagnostics, marginals, taxon-pair relations, WAIC, chain agreement, the central state, posterior predictive checks)
+ * address the rows they read, and those
  * analyses' entry points.  Plain C.  Included by sr_host.c, sr_records.hip and the analysis .hip files only: the
  * sweep kernel's sources (sr_device.hip, sr_internal.h; the snapshot sr_spec.c compiles from) know nothing of it.
  */
@@ -96,6 +97,15 @@ int src_central(const sr_recview *v, int N, int M, const uint8_t *flip, long lon
                 uint32_t *pair_counts, int32_t *best, int32_t *state, int32_t *chain, int32_t *row, float *ms);
 int src_order_loss(const sr_recview *v, int N, int M, const uint8_t *flip, const uint32_t *against,
                    long long *order_loss, float *ms);
+
+/* posterior predictive checks (sr_ppc.hip): exact integers, defined in include/seriation.h.  X, cd, cdw and manycd
+   as srw_waic takes them; reps in 1..64 and n_sel * count * reps < 2^31.  taxon_gt, taxon_eq, taxon_sum_obs,
+   taxon_sum_rep [5][M], site_gt, site_eq, site_sum_rep [N], total_obs [n_sel][count][5], total_rep
+   [n_sel][count][reps][5] are outputs, each optional; total_gt, total_eq [5] are always written */
+int srq_ppc(const sr_recview *v, int N, int M, const uint8_t *X, const double *const *cd, int cdw, int manycd,
+            uint64_t seed, int reps, uint32_t *taxon_gt, uint32_t *taxon_eq, long long *taxon_sum_obs,
+            long long *taxon_sum_rep, uint32_t *site_gt, uint32_t *site_eq, long long *site_sum_rep,
+            long long *total_obs, long long *total_rep, long long *total_gt, long long *total_eq, float *ms);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
                                     [--marginals] [--relations] [--waic] [--modes [--mode-threshold X]]
-                                    [--central]
+                                    [--central] [--ppc [--ppc-seed S] [--ppc-reps R]]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -28,6 +28,13 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 chain_data.csv, shared rates or, with --manycd, per-taxon rates).  Chains/waic.csv: one row
                 elpd_waic, se, p_waic, lppd, waic, n_high (cells with p_waic above 0.4), samples, cells;
                 Chains/waic_sites.csv and Chains/waic_taxa.csv: each site's and each taxon's share of elpd_waic
+  --ppc         with --select: posterior predictive checks of the chosen chains (analysis.ppc_from_records over their
+                chain_data.csv, shared rates or, with --manycd, per-taxon rates): --ppc-reps R (default 1, at most 64)
+                replicate matrices per saved sample, drawn with --ppc-seed S (default 0), against the data on five
+                discrepancies (ones, span, gaps, f0: false zeros, f1: false ones).  Chains/ppc.csv: per discrepancy
+                the mean total of the data and of the replicates, the p-value (gt + eq / 2) / pairs and its counts;
+                Chains/ppc_taxa.csv: the same means and p per taxon and discrepancy; Chains/ppc_sites.csv: per site
+                its number of taxa in the data, the replicates' mean and p
   --modes       which chains sampled the same order, over all chains of the run, before and independent of --select
                 (analysis.agreement_from_records and chain_modes over their chain_data.csv).  Chains/chain_modes.csv:
                 per chain its mode, its flip against the mode's first chain, whether it is the mode's medoid, the
@@ -100,6 +107,35 @@ def write_relations(ds, chains, root, device=0):
             for j in range(i + 1, ds.M):
                 fh.write("%d,%d,%d,%d,%d,%d,%d,%d,%d\n" % (i, j, ob[i][j], ob[j][i], eb[i][j], eb[j][i], pr[i][j],
                                                           pr[j][i], ov[i][j]))
+
+
+def write_ppc(ds, chains, root, manycd=False, seed=0, reps=1, device=0):
+    """Chains/ppc.csv, Chains/ppc_taxa.csv and Chains/ppc_sites.csv of the chosen chains: posterior predictive checks
+    over their chain_data.csv rows, the rates read back from the files' c and d tokens."""
+    import numpy as np
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    cd = analysis.read_chain_cd(root, chains, ds.M, manycd=manycd)
+    r = analysis.ppc_from_records(ds, rec, cd, manycd=manycd, seed=seed, reps=reps, device=device)
+    pairs = float(r["pairs"])
+    with open(os.path.join(root, "Chains", "ppc.csv"), "w") as fh:
+        fh.write("stat,obs_mean,rep_mean,p,gt,eq,pairs\n")
+        for i, name in enumerate(analysis.PPC_STATS):
+            fh.write("%s,%r,%r,%r,%d,%d,%d\n" % (name, float(int(r["taxon_sum_obs"][i].sum())) / pairs,
+                                                 float(int(r["taxon_sum_rep"][i].sum())) / pairs,
+                                                 float(r["p_total"][i]), r["total_gt"][i], r["total_eq"][i],
+                                                 r["pairs"]))
+    with open(os.path.join(root, "Chains", "ppc_taxa.csv"), "w") as fh:
+        fh.write("taxon,stat,obs_mean,rep_mean,p\n")
+        for m in range(ds.M):
+            for i, name in enumerate(analysis.PPC_STATS):
+                fh.write("%d,%s,%r,%r,%r\n" % (m, name, float(r["taxon_sum_obs"][i, m]) / pairs,
+                                               float(r["taxon_sum_rep"][i, m]) / pairs, float(r["p_taxon"][i, m])))
+    obs = np.ctypeslib.as_array(ds.c.X, (ds.N * ds.M,)).reshape(ds.N, ds.M).astype(bool).sum(axis=1)
+    with open(os.path.join(root, "Chains", "ppc_sites.csv"), "w") as fh:
+        fh.write("site,obs,rep_mean,p\n")
+        for n in range(ds.N):
+            fh.write("%d,%d,%r,%r\n" % (n, obs[n], float(r["site_sum_rep"][n]) / pairs, float(r["p_site"][n])))
 
 
 def write_waic(ds, chains, root, manycd=False, device=0):
@@ -191,6 +227,9 @@ def main(argv=None):
     ap.add_argument("--marginals", action="store_true")
     ap.add_argument("--relations", action="store_true")
     ap.add_argument("--waic", action="store_true")
+    ap.add_argument("--ppc", action="store_true")
+    ap.add_argument("--ppc-seed", type=int, default=0)
+    ap.add_argument("--ppc-reps", type=int, default=1)
     ap.add_argument("--modes", action="store_true")
     ap.add_argument("--mode-threshold", type=float, default=0.1)
     ap.add_argument("--central", action="store_true")
@@ -201,6 +240,10 @@ def main(argv=None):
         ap.error("--mode-threshold must lie in [0, 1]")
     if a.waic and (a.select < 1 or a.no_save):
         ap.error("--waic needs --select K (and the chain files: not with --no-save)")
+    if a.ppc and (a.select < 1 or a.no_save):
+        ap.error("--ppc needs --select K (and the chain files: not with --no-save)")
+    if a.ppc and not (1 <= a.ppc_reps <= 64 and 0 <= a.ppc_seed < 2 ** 64):
+        ap.error("--ppc-reps must lie in 1..64 and --ppc-seed in 0..2^64-1")
     if a.marginals and (a.select < 1 or a.no_save):
         ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
     if a.relations and (a.select < 1 or a.no_save):
@@ -246,6 +289,9 @@ def main(argv=None):
                 write_relations(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
             if a.waic:
                 write_waic(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, devices[0] if devices else 0)
+            if a.ppc:
+                write_ppc(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, a.ppc_seed, a.ppc_reps,
+                          devices[0] if devices else 0)
             if a.central:
                 print("central: chain %d row %d" % write_central(core.Dataset.load(a.dataset), chosen, a.root,
                                                                   devices[0] if devices else 0))

@@ -111,6 +111,17 @@ class sr_waic_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_ppc_out(ctypes.Structure):
+    _fields_ = [("taxon_gt", ctypes.POINTER(ctypes.c_uint32)), ("taxon_eq", ctypes.POINTER(ctypes.c_uint32)),
+                ("taxon_sum_obs", ctypes.POINTER(ctypes.c_int64)), ("taxon_sum_rep", ctypes.POINTER(ctypes.c_int64)),
+                ("site_gt", ctypes.POINTER(ctypes.c_uint32)), ("site_eq", ctypes.POINTER(ctypes.c_uint32)),
+                ("site_sum_rep", ctypes.POINTER(ctypes.c_int64)),
+                ("total_obs", ctypes.POINTER(ctypes.c_int64)), ("total_rep", ctypes.POINTER(ctypes.c_int64)),
+                ("total_gt", ctypes.c_int64 * 5), ("total_eq", ctypes.c_int64 * 5),
+                ("pairs", ctypes.c_int64),
+                ("kernel_ms", ctypes.c_double)]
+
+
 class sr_agree_out(ctypes.Structure):
     _fields_ = [("pair_counts", ctypes.POINTER(ctypes.c_uint32)),
                 ("dist", ctypes.POINTER(ctypes.c_int64)), ("dist_mirror", ctypes.POINTER(ctypes.c_int64)),
@@ -145,6 +156,7 @@ PUBLIC_SYMBOLS = [
     "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior",
     "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals",
     "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce",
+    "sr_ppc", "sr_session_ppc",
     "sr_agreement", "sr_session_agreement", "sr_agreement_distances", "sr_agreement_modes",
     "sr_central", "sr_session_central", "sr_order_loss",
     "sr_strerror", "sr_device_count", "sr_version",
@@ -217,6 +229,9 @@ def _lib():
         "sr_waic": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, c_i32, P(sr_waic_out)]),
         "sr_session_waic": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_waic_out)]),
         "sr_waic_reduce": (c_int, [c_i32, c_i32, P(c_double), P(c_double), P(sr_waic_out)]),
+        "sr_ppc": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, ctypes.c_uint64, c_i32,
+                           c_i32, P(sr_ppc_out)]),
+        "sr_session_ppc": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, ctypes.c_uint64, c_i32, P(sr_ppc_out)]),
         "sr_agreement": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_agree_out)]),
         "sr_session_agreement": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_agree_out)]),
         "sr_agreement_distances": (c_int, [c_i32, c_i32, P(ctypes.c_uint32), c_i32, P(ctypes.c_int64),

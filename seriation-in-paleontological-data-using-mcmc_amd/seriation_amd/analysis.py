@@ -483,6 +483,75 @@ def waic_compare(a, b):
     return {"elpd_diff": float(tot), "se_diff": float(se)}
 
 
+# ---------------------------------------------------------------- posterior predictive checks
+# Is the model adequate: for every saved sample, replicate matrices drawn from the model at that sample against X
+# under the same sample, on five discrepancies per taxon (ones, span, gaps, false zeros, false ones), the row sums
+# per site and the totals (definitions: include/seriation.h).  A p-value near 0 or 1 marks a taxon or site the model
+# misfits; the false zeros' is a per-taxon test of the shared rate d.  The draws and the tallies run on the GPU
+# (csrc/sr_ppc.hip); there is no CPU fallback.  Every count is an exact integer.
+PPC_STATS = ("ones", "span", "gaps", "f0", "f1")
+
+
+def ppc_pvalue(gt, eq, pairs):
+    """(gt + 0.5 * eq) / pairs in float64"""
+    return (np.asarray(gt, np.float64) + 0.5 * np.asarray(eq, np.float64)) / np.float64(pairs)
+
+
+def _ppc_outs(N, M, n_sel, count, reps, totals):
+    n, c, r = max(int(n_sel), 0), max(int(count), 0), max(int(reps), 0)
+    arrs = {"taxon_gt": np.zeros((5, M), np.uint32), "taxon_eq": np.zeros((5, M), np.uint32),
+            "taxon_sum_obs": np.zeros((5, M), np.int64), "taxon_sum_rep": np.zeros((5, M), np.int64),
+            "site_gt": np.zeros(N, np.uint32), "site_eq": np.zeros(N, np.uint32), "site_sum_rep": np.zeros(N, np.int64)}
+    if totals:
+        arrs["total_obs"] = np.zeros((n, c, 5), np.int64)
+        arrs["total_rep"] = np.zeros((n, c, r, 5), np.int64)
+    out = L.sr_ppc_out()
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data_as(_U32P if a.dtype == np.uint32 else _I64P))
+    return out, arrs
+
+
+def _ppc_result(out, arrs):
+    res = dict(arrs)
+    res["total_gt"] = np.array(list(out.total_gt), np.int64)
+    res["total_eq"] = np.array(list(out.total_eq), np.int64)
+    res["pairs"] = int(out.pairs)
+    res["kernel_ms"] = out.kernel_ms
+    res["p_taxon"] = ppc_pvalue(res["taxon_gt"], res["taxon_eq"], res["pairs"])
+    res["p_site"] = ppc_pvalue(res["site_gt"], res["site_eq"], res["pairs"])
+    res["p_total"] = ppc_pvalue(res["total_gt"], res["total_eq"], res["pairs"])
+    return res
+
+
+def ppc_from_records(dataset, ab_pi, cd, manycd=False, seed=0, reps=1, totals=False, device=0):
+    """sr_ppc: ab_pi [n_sel][count][2M+N] and the rates cd as waic_from_records takes them, seed any uint64, reps
+    1..64 replicates per sample -> {"taxon_gt", "taxon_eq" [5][M] uint32, "taxon_sum_obs", "taxon_sum_rep" [5][M]
+    int64 (rows in the order of PPC_STATS), "site_gt", "site_eq" [N], "site_sum_rep" [N], "total_gt", "total_eq"
+    [5], "pairs" = n_sel * count * reps, "kernel_ms", and the p-values (gt + 0.5 eq) / pairs: "p_taxon" [5][M],
+    "p_site" [N], "p_total" [5]}; totals adds "total_obs" [n_sel][count][5] and "total_rep" [n_sel][count][reps][5]."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    r = np.ascontiguousarray(cd, dtype=np.float64)
+    assert r.shape == (n_sel, count, 2 * dataset.M if manycd else 3)
+    out, arrs = _ppc_outs(dataset.N, dataset.M, n_sel, count, reps, totals)
+    _check(L.lib().sr_ppc(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)),
+                          r.ctypes.data_as(_DBLP), int(bool(manycd)), n_sel, count, int(seed), int(reps), device,
+                          ctypes.byref(out)), "sr_ppc")
+    return _ppc_result(out, arrs)
+
+
+def ppc_from_session(session, chains, first=0, count=None, seed=0, reps=1, totals=False):
+    """sr_session_ppc: the same over a session's records and rates still in HBM, rows [first, first + count) of
+    chains (session chain indices in selection order); shared or per-taxon rates as the session samples them."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs = _ppc_outs(session.ds.N, session.ds.M, len(chains), count, reps, totals)
+    _check(L.lib().sr_session_ppc(session.h, ch, len(chains), first, count, int(seed), int(reps), ctypes.byref(out)),
+           "sr_session_ppc")
+    return _ppc_result(out, arrs)
+
+
 # ---------------------------------------------------------------- chain agreement and modes
 # Which chains sampled the same order: per chain the exact counts of every site pair's order, the L1 distance between
 # every two chains' counts, plain and against the mirror image, and the single-linkage modes read off them
