@@ -1153,12 +1153,13 @@ __device__ __forceinline__ int walk_pick_s(const uint32_t (&wk)[NWM], const doub
     const double inv = 1.0 / S;
     const double REL = (double)(N + 33) * 0x1p-50 * SR_CERT_SCALE;   /* + the byte tables' own rounding (<= 16 ulp per entry) */
     const double ABS = (double)(N + 1) * 0x1p-39 * SR_CERT_SCALE;
-    /* the words before the window hold S = 0 (< u S), so counting k < khi finds the word */
+    /* the words before the window hold S = 0 (< u S), so counting k < khi finds the word (9-word walks have
+       no window: klo = 0, khi = the walk's last word) */
     const double uS = u * S;
     int j = 0;
 #pragma unroll
     for (int k = 0; k < NWM; ++k) j += (k < khi && ckr[k] < uS) ? 1 : 0;
-    j = max(j, klo);   /* (u = 0) */
+    if constexpr (NWM > 9) j = max(j, klo);   /* (u = 0) */
     double Sp0 = 0.0, y = yst[0];
     uint32_t ww = wk[0];
     [[maybe_unused]] int Oj = 0, Ok = 0;   /* ones among walk entries [0, 32 j) (9-word walks) */
@@ -1231,7 +1232,8 @@ __device__ __forceinline__ int walk_pick_s(const uint32_t (&wk)[NWM], const doub
 
 /* draw_fast with the walk words in registers, fully unrolled and branch-free (the measured cost
  * of a loop trip with a taken branch on gfx950 is ~36 cycles, more than the work it guards).
- * Same approximation and certification as draw_fast; fallback to draw_exact on failure. */
+ * Same approximation and certification as draw_fast; fallback to draw_exact on failure.  The 9-word
+ * walks (N <= 287) have no pass 0: they sum every word of the walk from a fixed scale. */
 template <int NWM>
 __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint32_t *Pm, int M, int N, bool rev, int o,
                                            int L, int POo, double u, const CD &K, const sr_mtab &tb, double vA, double vB,
@@ -1240,17 +1242,24 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
 {
   /* POo: ones among walk entries [0, o), from the caller's column prefix table */
   const int nk = (L >> 5) + 1;
-  /* pass 0: window of words that can hold mass above 2^-40 relative to entry o.  q at a word
-     start w0 is F(o) - F(w0), F(w) = zeros before w * vA + ones before w * vB = w vA + O(w) (vB - vA)
-     (the window only bounds the skipped mass: the pick is certified independently of it). */
   int klo = NWM, khi = -1;
   double qlo = 0.0;
   [[maybe_unused]] uint32_t lowm = 0u;   /* 17-word walks: words whose start q lies below -700 (pass 2) */
   const int kl = L >> 5, nbl = (L & 31) + 1;   /* the walk's last word and its entries */
   uint32_t wl = 0u;                              /* word kl */
-  {
-    const double dv = vB - vA;
-    const double Fo = __builtin_fma((double)POo, dv, (double)o * vA);
+  if constexpr (NWM <= 9) {
+    /* No pass 0 and no window: pass 1 is unrolled and branch-free, so a word outside a window would take its
+       step all the same (with the dead entry); the walk runs over all its words, [0, kl], from y = 1 at entry 0
+       (the scale and underflow argument: above pass 2). */
+    klo = 0;
+    khi = kl;
+#pragma unroll
+    for (int k = 0; k < NWM; ++k) wl |= wk[k] & (0u - (uint32_t)(k == kl));   /* (the select form spills more in
+                                                                                 the generic 512-thread kernel) */
+  } else {
+    /* pass 0: window of words that can hold mass above 2^-40 relative to entry o, from q at the word starts
+       by exact counts (the window only bounds the skipped mass: the pick is certified independently of it);
+       the two-sided form of q: the form F(o) - F(w0) spills here (+9 % kernel time at N = 400) */
     int O = 0;   /* ones among walk entries [0, 32k) */
     const uint32_t lastm = (2u << (L & 31)) - 1u;
 #pragma unroll
@@ -1258,27 +1267,22 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
       const bool full = k < kl;   /* (words past kl are outside the walk: not in the window) */
       const int nb = full ? 32 : nbl;
       const uint32_t vm = full ? 0xffffffffu : lastm;
-      double qs;
-      if constexpr (NWM <= 9) qs = Fo - __builtin_fma((double)O, dv, (double)(32 * k) * vA);
-      else {   /* the 17-word walks keep the two-sided form: the F form spills there (+9 % kernel time at N = 400) */
-        const int w0 = 32 * k;
-        qs = (w0 <= o) ? ((double)((o - w0) - (POo - O)) * vA + (double)(POo - O) * vB)
-                       : -((double)((w0 - o) - (O - POo)) * vA + (double)(O - POo) * vB);
-      }
+      const int w0 = 32 * k;
+      const double qs = (w0 <= o) ? ((double)((o - w0) - (POo - O)) * vA + (double)(POo - O) * vB)
+                                  : -((double)((w0 - o) - (O - POo)) * vA + (double)(O - POo) * vB);
       const int ones = __popc(wk[k] & vm);
       const double ub = qs - (double)(nb - ones) * vA;
       const bool in = (k < nk) && ub > -SR_WIN_T;
-      if constexpr (NWM > 9) lowm |= (qs < -700.0 ? 1u : 0u) << k;
+      lowm |= (qs < -700.0 ? 1u : 0u) << k;
       const bool first = in && klo == NWM;
       qlo = first ? qs : qlo;
       klo = first ? k : klo;
       khi = in ? k : khi;
       O += __popc(wk[k]);
-      if constexpr (NWM <= 9) wl = (k == kl) ? wk[k] : wl;
     }
   }
 #ifdef SR_STAMP_FINE
-  {   /* window statistics: words per draw, wave max, walk words */
+  {   /* window statistics: words per draw, wave max, walk words (9-word walks have no window: all nk words) */
     const int wn = khi - klo + 1;
     int wmax = wn;
     for (int off_ = 32; off_ > 0; off_ >>= 1) wmax = max(wmax, __shfl_xor(wmax, off_));
@@ -1297,17 +1301,19 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
      trailing, so W and the product stay exact for them); each entry's value keeps at most as many
      roundings as the byte-by-byte chain it replaces, inside REL.  The walk's partial last byte
      ((L + 1) mod 8 entries) follows from the 4-entry tables (T4 rows c = 0..4). */
-  const double y0 = exp2_split(qlo);
   double S = 0.0;
   double ckr[NWM], yst[NWM];
-  double y = y0;
+  double y = 1.0;   /* 9-word walks: scaled to walk entry 0 */
+  if constexpr (NWM > 9) y = exp2_split(qlo);
   {
     /* word k's 4 entries (whole bytes of the walk inside the window; the dead entry otherwise) */
     auto wload = [&](int k, double2 (&t)[4]) {
-      const bool inw = k >= klo && k <= khi;
       int nfk;   /* whole bytes of the walk in word k (khi <= kl) */
-      if constexpr (NWM <= 9) nfk = inw ? ((k < kl) ? 4 : (nbl >> 3)) : 0;
-      else nfk = inw ? min(max((L + 1 - 32 * k) >> 3, 0), 4) : 0;   /* (the form above is 1.8 % slower here) */
+      if constexpr (NWM <= 9) nfk = ((L + 1) >> 3) - 4 * k;   /* (<= 0 past the walk, >= 4 inside it) */
+      else {
+        const bool inw = k >= klo && k <= khi;
+        nfk = inw ? min(max((L + 1 - 32 * k) >> 3, 0), 4) : 0;   /* (the 9-word form is 1.8 % slower here) */
+      }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const uint32_t e = (g < nfk) ? ((wk[k] >> (8 * g)) & 255u) : 256u;
@@ -1339,12 +1345,15 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
       ckr[k] = S;
 #pragma unroll
       for (int g = 0; g < 4; ++g) t[g] = tn[g];
-      __builtin_amdgcn_sched_barrier(0);   /* one word of reads ahead, no more (register pressure; two words
-                                              ahead: 10 -> 19 VGPR spills, +0.7 %, profiles/r05r_ab_gibbs_ahead.json) */
+      __builtin_amdgcn_sched_barrier(0);   /* one word of reads ahead, no more (two words ahead: round 5, 10 -> 19
+                                              VGPR spills, +0.7 %, profiles/r05r_ab_gibbs_ahead.json; round 12, without
+                                              pass 0, no spill and -0.55 %, three baseline spreads: not kept,
+                                              profiles/r12a_ab_gibbs_ahead.json) */
     }
     /* the partial byte (c8 entries) when its word lies in the window */
     const int nfull = (L + 1) >> 3, c8 = (L + 1) & 7, kb = nfull >> 2;
-    const bool actb = c8 > 0 && kb >= klo && kb <= khi;
+    bool actb = c8 > 0;   /* (9-word walks: every word of the walk is summed) */
+    if constexpr (NWM > 9) actb = actb && kb >= klo && kb <= khi;
     uint32_t wb = wl;   /* word kb = kl when c8 > 0 (the 17-word kernel selects it here: tracking spills there) */
     if constexpr (NWM > 9) {
 #pragma unroll
@@ -1359,15 +1368,20 @@ __device__ __forceinline__ int draw_fast_s(const uint32_t (&wk)[NWM], const uint
   /* pass 2: locate the word, then the byte, nibble and entry where u falls (the searches compare
      against u S; the pick is certified below, independently of how it was found) */
   int res = -1, POp = 0;   /* the pick and the ones among walk entries [0, pick) */
-  /* Underflow: y at a window word start is 2^q up to rounding, and a chain that sank into the
-     subnormal range would lose its relative precision.  Only zeros raise q (by |vA| each) and the
-     window's last word reaches q > -40, so every window word start lies above -40 - 32 nk |vA|;
-     d >= 0.2 and c <= 0.1 always (mcmc_samplebeta's bounds MIND / MAXC, mcmc.h:27-30; the initial
-     values log .01 / log .3, mcmc.c:419-420) give |vA| = log2((1 - c) / d) <= log2 5 = 2.33.  Walks of
-     <= 9 words therefore stay above 2^-710 and next words' y above 2^-1018 (a word's product is
-     >= 2^-32 vB >= 2^-309): no test.  17-word walks can sink further: a window word start below
-     2^-700 sends the draw to the exact path (pass 0's exact q, a bit mask; a per-draw test costs
-     2 % of the 9-word kernel, profiles/r03n_ab_yguard.json). */
+  /* Scale and underflow of the 9-word walks (N <= 287 only), which have no window and start from y = 1 at walk
+     entry 0; the common factor cancels in the CDF.  A zero raises y by rA = 2^-vA and a one lowers it; d >= 0.2
+     and c <= 0.1 always (mcmc_samplebeta's bounds MIND / MAXC, mcmc.h:27-30; the initial values log .01 /
+     log .3, mcmc.c:419-420) give -vA = log2((1 - c) / d) <= log2 5 = 2.322.  A walk has at most N + 1 <= 288
+     entries, so every y is <= 2^(2.322 * 287) < 2^667 and S < 2^676: nothing overflows, and S >= y(0) = 1, so
+     the test of S below cannot fail.  A chain may sink below 2^-1022 (after >= 106 ones) and lose its relative
+     precision there, but every y downstream of such a value is at most 2^-1022 * 2^667 = 2^-355, and so is its
+     true value: against S >= 1 these entries, precise or not, move the CDF by far less than ABS = (N + 1) 2^-39.
+     Entries whose chain never dipped keep the relative accuracy of REL.  No word is skipped, so the skipped-mass
+     term of the error model is zero.  Longer walks cannot take a fixed scale: after sinking into the subnormals
+     a 17-word chain can rise by 2^(2.322 * 499) > 2^1022, and imprecise values could carry real mass.  They keep
+     the window, which puts every window word start above -40 - 32 nk |vA|, and a window word start below
+     2^-700 sends the draw to the exact path (pass 0's exact q, a bit mask; a per-draw test costs 2 % of the
+     9-word kernel, profiles/r03n_ab_yguard.json). */
   bool yok = true;
   if constexpr (NWM > 9) yok = klo > khi || (lowm & ((2u << khi) - 1u) & ~((1u << klo) - 1u)) == 0u;
   if (S > 0.0 && S < 0x1p1000 && yok) res = walk_pick_s<NWM>(wk, ckr, yst, S, klo, khi, L, N, u, T4, T8, POp);
