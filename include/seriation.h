@@ -413,6 +413,77 @@ int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t
 /* the reduction alone, on the host: scalars, site_elpd and taxon_elpd of out from lppd, pwaic [N][M] */
 int sr_waic_reduce(int32_t N, int32_t M, const double *lppd, const double *pwaic, sr_waic_out *out);
 
+/* ---- PSIS-LOO: leave-one-out cross-validation by Pareto-smoothed importance sampling, and the Pareto shape per
+ * cell, over saved samples: defined to the bit ----
+ * (an extension: the estimator Vehtari, Gelman & Gabry 2017 recommend over WAIC for the same quantity; the shape
+ * estimate k says where it can be trusted.  For this model a cell with large k is an occurrence, or an absence,
+ * whose likelihood is carried by a handful of samples: a presence far outside its taxon's range, or a gap inside
+ * it.)  Inputs exactly as sr_waic: ds, ab_pi, cd, manycd, n_sel, count; T = n_sel * count, sample (k, r) and the cell
+ * index 0..3 as there.  No flip input: a reflected chain changes no alive bit and no output.
+ * Table, per sample (and per taxon when manycd), with this library's exp: p = {1.0 - ec, ed, 1.0 - ed, ec} as in
+ * WAIC; r[j] = 1.0 / p[j], one IEEE division per table entry.
+ * Per cell, sums over samples in WAIC's order (within chain k sequentially over r ascending from +0.0, then the
+ * chain sums over k ascending from +0.0; no fma, no floating-point atomics): Sp the sum of p, Sr the sum of r;
+ * lppd = log(Sp / (double)T), bit-equal to sr_waic's.
+ * Tail length, in integers: n = min(T / 5, s), s the smallest integer with s * s >= 9 T (loo's min(0.2 T, 3 sqrt T)
+ * with the rounding fixed).
+ * Tail: y_1 <= ... <= y_n the n largest of the cell's T values r, as a sorted multiset; r_cut the (n+1)-th largest;
+ * x_j = y_j - r_cut.  Nothing depends on which of several equal samples is taken.
+ * Host tables, computed once per call with the C library's sqrt and log: m = 30 + isqrt(n);
+ *   G_j = (1.0 - sqrt((double)m / ((double)j - 0.5))) / 3.0, j = 1..m;
+ *   L_j = log(1.0 - ((double)j - 0.5) / (double)n), j = 1..n.
+ * Fit (Zhang & Stephens 2009 as in loo 2.x gpdfit, log1p(-z) written log(1.0 - z)); every sum sequential ascending
+ * from +0.0, every product rounded before it is added, nd = (double)n, exp and log this library's:
+ *   xs = x_q, q = (n + 2) / 4 (integer division, 1-based);  theta_j = 1.0 / x_n + G_j / xs;
+ *   k_j = (sum_i log(1.0 - theta_j * x_i)) / nd;  l_j = nd * ((log(-theta_j / k_j) - k_j) - 1.0);
+ *   lmax = max_j l_j;  w_j = exp(l_j - lmax);  z = sum_j w_j;  th = sum_j theta_j * (w_j / z);
+ *   k0 = (sum_i log(1.0 - th * x_i)) / nd;  sigma = -k0 / th;  k = (k0 * nd + 5.0) / (nd + 10.0) (the weakly
+ *   informative prior of loo >= 2.0).
+ * Unsmoothed cases: n < 5 (T < 25); !(xs > 0.0) (ties reaching the first quartile of the tail); any of l_j, th, k0,
+ * sigma, k not finite.  Then pareto_k = +inf and elpd_loo = log((double)T / Sr), plain importance-sampling LOO.
+ * Smoothed tail: s_j = r_cut + (sigma * (exp(-k * L_j) - 1.0)) / k, or r_cut - sigma * L_j if k == 0.0;
+ *   wt_j = s_j if s_j < y_n, else y_n (loo's truncation at the largest raw ratio; it absorbs an overflowing exp);
+ *   St = sum_j y_j, Sw = sum_j wt_j, Nn = sum_j wt_j / y_j, D = (Sr - St) + Sw;
+ *   elpd_loo = log(((double)(T - n) + Nn) / D).
+ * (A non-tail sample contributes weight r_t and weight x likelihood exactly 1: PSIS-LOO in the linear domain, with
+ * no sort of the non-tail values.)
+ * Pointwise, [N][M] f64, each optional: elpd_loo, pareto_k, lppd, p_loo_i = lppd_i - elpd_loo_i (formed on the host).
+ * Reduction (plain C on the host; sr_loo_reduce runs it alone on given arrays): sr_waic_reduce's formulas with
+ * e_i = elpd_loo_i: elpd, lppd_sum and p_loo the sequential row-major sums of e_i, lppd_i and lppd_i - e_i; se from me
+ * and Q as there; looic = -2.0 * elpd; site_elpd [N], taxon_elpd [M]; n_k[4] the cells with k <= 0.5, 0.5 < k <= 0.7,
+ * 0.7 < k <= 1, and k > 1 including +inf; tail_len = n (sr_loo and sr_session_loo only).
+ * sr_loo_tail is the tail alone on the host, the source the device runs: y [n] ascending, r_cut, Sr -> *k, *elpd; it
+ * sorts nothing.  sr_loo_tail_len(T) is n (0 for T outside 1..2^31-1).
+ * SR_EINVAL as sr_waic, but the rate domain is [-600, -2^-50]: with it every r <= e^600 and every sum over T < 2^31
+ * values is finite.  SR_EUNSUPPORTED: N M > 2^27; n > 4096 (T above about 1.86 M); a library built without the
+ * device layer.  All reported before any kernel runs, the outputs untouched.  Device scratch is bounded by
+ * SR_LOO_SCRATCH bytes (environment, default 256 MiB) each of per-chain partial sums, of table rows and of the cells'
+ * n + 1 largest ratios (cells are taken in batches, each batch re-reads the rows); the results do not depend on it. */
+typedef struct {
+  double *elpd_loo, *pareto_k, *lppd, *p_loo_i;   /* out: [N][M] each, NULL = skip */
+  double *site_elpd, *taxon_elpd;                 /* out: [N], [M], NULL = skip */
+  double elpd, se, p_loo, lppd_sum, looic;
+  int64_t n_k[4];
+  int32_t tail_len;
+  double kernel_ms;
+  double phase_ms[3];                             /* kernel_ms by phase: the sums, the selection, the finish */
+} sr_loo_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M and X */
+int sr_loo(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel, int32_t count,
+           int32_t device, sr_loo_out *out);
+/* the session's own records and rates in HBM, rows [first, first+count) of chains[] (selection order), on the
+   session's stream; manycd is the session's; the session's state and records are left untouched */
+int sr_session_loo(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                   sr_loo_out *out);
+/* the reduction alone, on the host: scalars (not tail_len), n_k, site_elpd and taxon_elpd of out from [N][M] arrays */
+int sr_loo_reduce(int32_t N, int32_t M, const double *lppd, const double *elpd_loo, const double *pareto_k,
+                  sr_loo_out *out);
+/* one cell's tail alone, on the host: SR_EINVAL for NULL k or elpd, T outside 1..2^31-1, n < 0, n >= T (n > 0), NULL y
+   with n > 0; SR_EUNSUPPORTED for n > 4096 */
+int sr_loo_tail(int64_t T, int32_t n, const double *y, double r_cut, double Sr, double *k, double *elpd);
+int32_t sr_loo_tail_len(int64_t T);
+
 /* ---- Posterior predictive checks over saved samples: exact integers, the replicates defined to the bit ----
  * (an extension: WAIC ranks the two rate models against each other; whether the preferred one is adequate -- one
  * false-zero rate for every taxon, no per-site sampling effort -- is a posterior predictive check on realised

@@ -28,6 +28,7 @@
 #include "sr_internal.h"
 #include "sr_records.h"
 #include "sr_math.h"
+#include "sr_psis.h"
 #include "sr_rng.h"
 
 #define SR_API __attribute__((visibility("default")))
@@ -1051,7 +1052,7 @@ static double *post_slot(sr_posterior_out *o, int k)
 
 /* ---- the record view of the analyses below (sr_records.h) ---- */
 /* The view's functions (sr_records.hip) and the analyses' entry points (sr_post, sr_diag, sr_marg, sr_rel, sr_agree,
-   sr_waic, sr_central, sr_ppc .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
+   sr_waic, sr_loo, sr_central, sr_ppc .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
    every analysis reports SR_EUNSUPPORTED, after its argument checks and before anything is uploaded. */
 #define SR_WEAK(f) extern __typeof__(f) f __attribute__((weak))
 SR_WEAK(sr_recview_host);
@@ -1064,6 +1065,7 @@ SR_WEAK(srr_relations);
 SR_WEAK(sra_agreement);
 SR_WEAK(sra_distances_host);
 SR_WEAK(srw_waic);
+SR_WEAK(srl_loo);
 SR_WEAK(src_central);
 SR_WEAK(src_order_loss);
 SR_WEAK(srq_ppc);
@@ -1801,6 +1803,184 @@ SR_API int sr_session_waic(sr_session *s, const int32_t *chains, int32_t n_sel, 
     if (!rc && !waic_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
   }
   if (!rc) rc = waic_run(&v, &s->ds, out, rows, cdw, manycd);
+  sr_recview_release(&v);
+  free(rows);
+  free(buf);
+  return rc;
+}
+
+/* ---- PSIS-LOO cross-validation and the Pareto shape per cell (definitions: include/seriation.h) ---- */
+SR_API int32_t sr_loo_tail_len(int64_t T)
+{
+  if (T < 1 || T >= ((int64_t)1 << 31)) return 0;
+  return sr_psis_tail_len(T);
+}
+
+/* the host tables of the fit: G [m], m = 30 + isqrt(n), and L [n], in one block the caller frees; n in 5..4096 */
+static double *loo_tables(int32_t n, int32_t *m_out)
+{
+  const int32_t m = 30 + sr_psis_isqrt(n);
+  double *G = (double *)malloc(sizeof(double) * ((size_t)m + n));
+  if (!G) return NULL;
+  double *L = G + m;
+  for (int32_t j = 1; j <= m; j++) G[j - 1] = (1.0 - sqrt((double)m / ((double)j - 0.5))) / 3.0;
+  for (int32_t j = 1; j <= n; j++) L[j - 1] = log(1.0 - ((double)j - 0.5) / (double)n);
+  *m_out = m;
+  return G;
+}
+
+SR_API int sr_loo_tail(int64_t T, int32_t n, const double *y, double r_cut, double Sr, double *k, double *elpd)
+{
+  if (!k || !elpd || T < 1 || T >= ((int64_t)1 << 31) || n < 0 || n >= T + (n == 0) || (n > 0 && !y)) return SR_EINVAL;
+  if (n > SR_PSIS_NMAX) return SR_EUNSUPPORTED;
+  int32_t m = 0;
+  double *G = NULL;
+  if (n >= 5 && !(G = loo_tables(n, &m))) return SR_ENOMEM;
+  sr_psis_tail(y, 1, n, r_cut, Sr, T, G, m, G ? G + m : NULL, &SR_HOST_TAB, k, elpd);
+  free(G);
+  return SR_OK;
+}
+
+SR_API int sr_loo_reduce(int32_t N, int32_t M, const double *lppd, const double *elpd_loo, const double *pareto_k,
+                         sr_loo_out *out)
+{
+  if (!lppd || !elpd_loo || !pareto_k || !out || N < 1 || M < 1) return SR_EINVAL;
+  const int64_t nm = (int64_t)N * M;
+  double sl = 0.0, sp = 0.0, se = 0.0, Q = 0.0;
+  int64_t nk[4] = {0, 0, 0, 0};
+  for (int64_t i = 0; i < nm; i++) {
+    const double k = pareto_k[i];
+    sl += lppd[i];
+    sp += lppd[i] - elpd_loo[i];
+    se += elpd_loo[i];
+    nk[k <= 0.5 ? 0 : (k <= 0.7 ? 1 : (k <= 1.0 ? 2 : 3))]++;
+  }
+  const double me = se / (double)nm;
+  for (int64_t i = 0; i < nm; i++) {
+    const double dv = elpd_loo[i] - me;
+    Q += dv * dv;
+  }
+  out->lppd_sum = sl;
+  out->p_loo = sp;
+  out->elpd = se;
+  out->looic = -2.0 * se;
+  out->se = sqrt((double)nm * (Q / (double)(nm - 1)));
+  for (int j = 0; j < 4; j++) out->n_k[j] = nk[j];
+  if (out->site_elpd)
+    for (int32_t n = 0; n < N; n++) {
+      double a = 0.0;
+      for (int32_t m = 0; m < M; m++) a += elpd_loo[(int64_t)n * M + m];
+      out->site_elpd[n] = a;
+    }
+  if (out->taxon_elpd)
+    for (int32_t m = 0; m < M; m++) {
+      double a = 0.0;
+      for (int32_t n = 0; n < N; n++) a += elpd_loo[(int64_t)n * M + m];
+      out->taxon_elpd[m] = a;
+    }
+  return SR_OK;
+}
+
+/* the argument checks both forms share, made before any device call */
+static int loo_check(const sr_loo_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (!out || n_sel <= 0 || count < 1 || (int64_t)n_sel * count < 2 || (int64_t)n_sel * count >= ((int64_t)1 << 31))
+    return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  return SR_OK;
+}
+
+/* what is refused though the arguments are in order: the matrix or the tail too large, no kernels in this build */
+static int loo_refuse(int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  return (int64_t)N * M > WAIC_CELLS_MAX || sr_psis_tail_len((int64_t)n_sel * count) > SR_PSIS_NMAX || !srl_loo
+           ? SR_EUNSUPPORTED : SR_OK;
+}
+
+/* every c, d that will be read lies in [-600, -2^-50] (NaN fails): rows as waic_cd_ok takes them */
+static int loo_cd_ok(const double *cd, int32_t count, int cdw, int Mt)
+{
+  for (int64_t r = 0; r < count; r++)
+    for (int j = 0; j < 2 * Mt; j++) {
+      const double v = cd[r * cdw + j];
+      if (!(v >= -600.0 && v <= -0x1p-50)) return 0;
+    }
+  return 1;
+}
+
+/* the pointwise arrays the caller did not ask for are temporaries here: the reduction needs lppd, elpd_loo and k */
+static int loo_run(const sr_recview *v, const sr_dataset *ds, sr_loo_out *out, const double *const *cd, int cdw,
+                   int manycd)
+{
+  const int N = ds->N, M = ds->M;
+  const size_t nm = (size_t)N * M;
+  const int32_t n = sr_psis_tail_len((int64_t)v->n_sel * v->count);
+  int32_t m = 0;
+  double *G = n >= 5 ? loo_tables(n, &m) : NULL;
+  double *lp = out->lppd ? out->lppd : (double *)malloc(nm * sizeof(double));
+  double *el = out->elpd_loo ? out->elpd_loo : (double *)malloc(nm * sizeof(double));
+  double *pk = out->pareto_k ? out->pareto_k : (double *)malloc(nm * sizeof(double));
+  int rc = (lp && el && pk && (G || n < 5)) ? SR_OK : SR_ENOMEM;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  if (!rc) rc = sr_code_of(srl_loo(v, N, M, ds->X, cd, cdw, manycd, n, m, G, G ? G + m : NULL, lp, el, pk, ms));
+  if (!rc) {
+    rc = sr_loo_reduce(N, M, lp, el, pk, out);
+    if (out->p_loo_i)
+      for (size_t i = 0; i < nm; i++) out->p_loo_i[i] = lp[i] - el[i];
+    out->tail_len = n;
+    for (int j = 0; j < 3; j++) out->phase_ms[j] = ms[j];
+    out->kernel_ms = (double)ms[0] + (double)ms[1] + (double)ms[2];
+  }
+  if (lp != out->lppd) free(lp);
+  if (el != out->elpd_loo) free(el);
+  if (pk != out->pareto_k) free(pk);
+  free(G);
+  return rc;
+}
+
+SR_API int sr_loo(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel,
+                  int32_t count, int32_t device, sr_loo_out *out)
+{
+  if (!ds || !ab_pi || !cd) return SR_EINVAL;
+  int rc = loo_check(out, n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!ds->X) return SR_EINVAL;
+  const int Mt = manycd ? ds->M : 1, cdw = manycd ? 2 * ds->M : 3;
+  if (!loo_cd_ok(cd, (int32_t)((int64_t)n_sel * count), cdw, Mt)) return SR_EINVAL;
+  if ((rc = loo_refuse(n_sel, count, ds->N, ds->M))) return rc;
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  if (!rows) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) rows[k] = cd + (size_t)k * count * cdw;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = loo_run(&v, ds, out, rows, cdw, manycd != 0);
+  sr_recview_release(&v);
+  free(rows);
+  return rc;
+}
+
+SR_API int sr_session_loo(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                          sr_loo_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = loo_check(out, n_sel, count, s->ds.N, s->ds.M);
+  if (rc) return rc;
+  sr_recview v;
+  rc = session_view(s, chains, n_sel, first, count, loo_refuse(n_sel, count, s->ds.N, s->ds.M), &v);
+  if (rc) return rc;
+  const int M = s->ds.M, manycd = s->opts.manycd != 0;
+  const int Mt = manycd ? M : 1, cdw = manycd ? 2 * M : 3;
+  /* the rates come to the host as sr_session_waic fetches them */
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  double *buf = (double *)malloc(sizeof(double) * (size_t)(manycd ? s->nchains : n_sel) * count * cdw);
+  rc = (rows && buf) ? SR_OK : SR_ENOMEM;
+  if (!rc && manycd && srk_fetch_cdv(s->dev, first, count, buf)) rc = SR_EDEVICE;
+  for (int k = 0; k < n_sel && !rc; k++) {
+    rows[k] = buf + (size_t)(manycd ? chains[k] : k) * count * cdw;
+    if (!manycd && srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, (double *)rows[k])) rc = SR_EDEVICE;
+    if (!rc && !loo_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
+  }
+  if (!rc) rc = loo_run(&v, &s->ds, out, rows, cdw, manycd);
   sr_recview_release(&v);
   free(rows);
   free(buf);

@@ -1,6 +1,6 @@
 /*
  * sr_records.h -- the record view: how the analyses over saved records (posterior summaries, convergence
- * diagnostics, marginals, taxon-pair relations, WAIC, chain agreement, the central state, posterior predictive checks)
+ * diagnostics, marginals, taxon-pair relations, WAIC, PSIS-LOO, chain agreement, the central state, posterior predictive checks)
  * address the rows they read, and those
  * analyses' entry points.  Plain C.  Included by sr_host.c, sr_records.hip and the analysis .hip files only: the
  * sweep kernel's sources (sr_device.hip, sr_internal.h; the snapshot sr_spec.c compiles from) know nothing of it.
@@ -81,6 +81,12 @@ int srr_relations(const sr_recview *v, int N, int M, const uint8_t *flip, uint32
    value already checked against the domain */
 int srw_waic(const sr_recview *v, int N, int M, const uint8_t *X, const double *const *cd, int cdw, int manycd,
              double *lppd, double *ll_mean, double *pwaic, float *ms);
+/* PSIS-LOO's pointwise terms (sr_loo.hip): lppd, elpd, pareto_k [N][M], as include/seriation.h defines them.  X, cd,
+   cdw and manycd as srw_waic takes them; n the tail length of T = n_sel * count (at most 4096), G [m] and L [n] the
+   host tables of the fit (not read when n < 5); ms3 [3] (optional) the kernels' time of the sum, the selection and
+   the finish phase */
+int srl_loo(const sr_recview *v, int N, int M, const uint8_t *X, const double *const *cd, int cdw, int manycd, int n,
+            int m, const double *G, const double *L, double *lppd, double *elpd, double *pareto_k, float *ms3);
 /* chain agreement (sr_agree.hip): pair_counts [n_sel][N][N], dist and dist_mirror [n_sel][n_sel] (only the pi part of
    a row is read), exact integers, each optional.  sra_distances_host is the reduction alone, from pair counts in
    host memory (any uint32 values): it reads no records and takes no view. */

@@ -7,7 +7,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
     python -m seriation_amd DATASET [--chains 100] [--burnin 1000] [--samples 1000] [--thin 10]
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
-                                    [--marginals] [--relations] [--waic] [--modes [--mode-threshold X]]
+                                    [--marginals] [--relations] [--waic] [--loo] [--modes [--mode-threshold X]]
                                     [--central] [--ppc [--ppc-seed S] [--ppc-reps R]]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
@@ -28,6 +28,12 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 chain_data.csv, shared rates or, with --manycd, per-taxon rates).  Chains/waic.csv: one row
                 elpd_waic, se, p_waic, lppd, waic, n_high (cells with p_waic above 0.4), samples, cells;
                 Chains/waic_sites.csv and Chains/waic_taxa.csv: each site's and each taxon's share of elpd_waic
+  --loo         with --select: PSIS-LOO cross-validation of the chosen chains (analysis.loo_from_records over their
+                chain_data.csv, shared rates or, with --manycd, per-taxon rates).  Chains/loo.csv: one row elpd_loo,
+                se, p_loo, lppd, looic, the cells with Pareto k <= 0.5, <= 0.7, <= 1 and above, the tail length,
+                samples, cells; Chains/loo_sites.csv and Chains/loo_taxa.csv: each site's and each taxon's share of
+                elpd_loo; Chains/loo_cells.csv: site, taxon, x, pareto_k, elpd_loo, lppd of the cells with k > 0.7 --
+                the occurrences, and absences, to recheck
   --ppc         with --select: posterior predictive checks of the chosen chains (analysis.ppc_from_records over their
                 chain_data.csv, shared rates or, with --manycd, per-taxon rates): --ppc-reps R (default 1, at most 64)
                 replicate matrices per saved sample, drawn with --ppc-seed S (default 0), against the data on five
@@ -157,6 +163,32 @@ def write_waic(ds, chains, root, manycd=False, device=0):
                 fh.write("%d,%r\n" % (i, float(r[key + "_elpd"][i])))
 
 
+def write_loo(ds, chains, root, manycd=False, device=0):
+    """Chains/loo.csv, Chains/loo_sites.csv, Chains/loo_taxa.csv and Chains/loo_cells.csv of the chosen chains:
+    PSIS-LOO over their chain_data.csv rows, the rates read back from the files' c and d tokens."""
+    import numpy as np
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    cd = analysis.read_chain_cd(root, chains, ds.M, manycd=manycd)
+    r = analysis.loo_from_records(ds, rec, cd, manycd=manycd, device=device)
+    with open(os.path.join(root, "Chains", "loo.csv"), "w") as fh:
+        fh.write("elpd_loo,se,p_loo,lppd,looic,k_le_0.5,k_le_0.7,k_le_1,k_gt_1,tail,samples,cells\n")
+        fh.write("%r,%r,%r,%r,%r,%d,%d,%d,%d,%d,%d,%d\n" % (
+            (float(r["elpd_loo"]), float(r["se"]), float(r["p_loo"]), float(r["lppd_sum"]), float(r["looic"]))
+            + tuple(r["n_k"]) + (r["tail_len"], r["total"], ds.N * ds.M)))
+    for name, key, n in (("loo_sites.csv", "site", ds.N), ("loo_taxa.csv", "taxon", ds.M)):
+        with open(os.path.join(root, "Chains", name), "w") as fh:
+            fh.write("%s,elpd\n" % key)
+            for i in range(n):
+                fh.write("%d,%r\n" % (i, float(r[key + "_elpd"][i])))
+    X = np.ctypeslib.as_array(ds.c.X, (ds.N * ds.M,)).reshape(ds.N, ds.M)
+    with open(os.path.join(root, "Chains", "loo_cells.csv"), "w") as fh:
+        fh.write("site,taxon,x,pareto_k,elpd_loo,lppd\n")
+        for n, m in zip(*np.nonzero(r["pareto_k"] > 0.7)):
+            fh.write("%d,%d,%d,%r,%r,%r\n" % (n, m, X[n, m] != 0, float(r["pareto_k"][n, m]), float(r["elpd"][n, m]),
+                                              float(r["lppd"][n, m])))
+
+
 def write_modes(ds, chains, root, threshold, device=0):
     """Chains/chain_modes.csv and Chains/chain_distances.csv of all the run's chains: the order distances between
     their chain_data.csv rows and the modes linked at `threshold`.  Returns the modes' sizes."""
@@ -227,6 +259,7 @@ def main(argv=None):
     ap.add_argument("--marginals", action="store_true")
     ap.add_argument("--relations", action="store_true")
     ap.add_argument("--waic", action="store_true")
+    ap.add_argument("--loo", action="store_true")
     ap.add_argument("--ppc", action="store_true")
     ap.add_argument("--ppc-seed", type=int, default=0)
     ap.add_argument("--ppc-reps", type=int, default=1)
@@ -240,6 +273,8 @@ def main(argv=None):
         ap.error("--mode-threshold must lie in [0, 1]")
     if a.waic and (a.select < 1 or a.no_save):
         ap.error("--waic needs --select K (and the chain files: not with --no-save)")
+    if a.loo and (a.select < 1 or a.no_save):
+        ap.error("--loo needs --select K (and the chain files: not with --no-save)")
     if a.ppc and (a.select < 1 or a.no_save):
         ap.error("--ppc needs --select K (and the chain files: not with --no-save)")
     if a.ppc and not (1 <= a.ppc_reps <= 64 and 0 <= a.ppc_seed < 2 ** 64):
@@ -289,6 +324,8 @@ def main(argv=None):
                 write_relations(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
             if a.waic:
                 write_waic(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, devices[0] if devices else 0)
+            if a.loo:
+                write_loo(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, devices[0] if devices else 0)
             if a.ppc:
                 write_ppc(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, a.ppc_seed, a.ppc_reps,
                           devices[0] if devices else 0)

@@ -111,6 +111,18 @@ class sr_waic_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_loo_out(ctypes.Structure):
+    _fields_ = [("elpd_loo", ctypes.POINTER(ctypes.c_double)), ("pareto_k", ctypes.POINTER(ctypes.c_double)),
+                ("lppd", ctypes.POINTER(ctypes.c_double)), ("p_loo_i", ctypes.POINTER(ctypes.c_double)),
+                ("site_elpd", ctypes.POINTER(ctypes.c_double)), ("taxon_elpd", ctypes.POINTER(ctypes.c_double)),
+                ("elpd", ctypes.c_double), ("se", ctypes.c_double), ("p_loo", ctypes.c_double),
+                ("lppd_sum", ctypes.c_double), ("looic", ctypes.c_double),
+                ("n_k", ctypes.c_int64 * 4),
+                ("tail_len", ctypes.c_int32),
+                ("kernel_ms", ctypes.c_double),
+                ("phase_ms", ctypes.c_double * 3)]
+
+
 class sr_ppc_out(ctypes.Structure):
     _fields_ = [("taxon_gt", ctypes.POINTER(ctypes.c_uint32)), ("taxon_eq", ctypes.POINTER(ctypes.c_uint32)),
                 ("taxon_sum_obs", ctypes.POINTER(ctypes.c_int64)), ("taxon_sum_rep", ctypes.POINTER(ctypes.c_int64)),
@@ -156,6 +168,7 @@ PUBLIC_SYMBOLS = [
     "sr_session_destroy", "sr_specialize", "sr_posterior", "sr_session_posterior",
     "sr_diagnostics", "sr_session_diagnostics", "sr_diag_reduce", "sr_marginals", "sr_session_marginals",
     "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce",
+    "sr_loo", "sr_session_loo", "sr_loo_reduce", "sr_loo_tail", "sr_loo_tail_len",
     "sr_ppc", "sr_session_ppc",
     "sr_agreement", "sr_session_agreement", "sr_agreement_distances", "sr_agreement_modes",
     "sr_central", "sr_session_central", "sr_order_loss",
@@ -229,6 +242,11 @@ def _lib():
         "sr_waic": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, c_i32, P(sr_waic_out)]),
         "sr_session_waic": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_waic_out)]),
         "sr_waic_reduce": (c_int, [c_i32, c_i32, P(c_double), P(c_double), P(sr_waic_out)]),
+        "sr_loo": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, c_i32, P(sr_loo_out)]),
+        "sr_session_loo": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_loo_out)]),
+        "sr_loo_reduce": (c_int, [c_i32, c_i32, P(c_double), P(c_double), P(c_double), P(sr_loo_out)]),
+        "sr_loo_tail": (c_int, [ctypes.c_int64, c_i32, P(c_double), c_double, c_double, P(c_double), P(c_double)]),
+        "sr_loo_tail_len": (c_i32, [ctypes.c_int64]),
         "sr_ppc": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, ctypes.c_uint64, c_i32,
                            c_i32, P(sr_ppc_out)]),
         "sr_session_ppc": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, ctypes.c_uint64, c_i32, P(sr_ppc_out)]),

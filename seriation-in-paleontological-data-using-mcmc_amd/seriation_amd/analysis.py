@@ -470,7 +470,9 @@ def waic_compare(a, b):
     """Two WAIC results with pointwise arrays of equal shape (one dataset, e.g. shared rates against manycd) ->
     {"elpd_diff": the sequential row-major sum of a.elpd_i - b.elpd_i (positive: a fits better), "se_diff":
     sqrt(n * (Q / (n - 1))), Q the sequential sum of (diff_i - elpd_diff / n)^2, n the number of cells (NaN when
-    n = 1)}: sr_waic_reduce's two-pass formula on the differences, host numpy."""
+    n = 1)}: sr_waic_reduce's two-pass formula on the differences, host numpy.  Only the pointwise array "elpd" is
+    read, and a PSIS-LOO result (loo_from_records, loo_from_session) carries its elpd_loo array under that name: two
+    LOO results, or a LOO and a WAIC result, compare the same way."""
     ea, eb = np.asarray(a["elpd"], np.float64), np.asarray(b["elpd"], np.float64)
     assert ea.shape == eb.shape and ea.size >= 1
     d = (ea - eb).reshape(-1)
@@ -481,6 +483,66 @@ def waic_compare(a, b):
     with np.errstate(invalid="ignore", divide="ignore"):
         se = np.sqrt(np.float64(n) * (q / np.float64(n - 1.0)))
     return {"elpd_diff": float(tot), "se_diff": float(se)}
+
+
+# ---------------------------------------------------------------- PSIS-LOO and the Pareto shape per cell
+# The same question as WAIC by the estimator recommended over it: leave-one-out cross-validation by Pareto-smoothed
+# importance sampling, every output defined to the bit (definitions: include/seriation.h).  pareto_k says where the
+# estimate can be trusted; a cell above 0.7 is an occurrence, or an absence, whose likelihood is carried by a handful
+# of samples -- the identifications to recheck first.  The sums, the per-cell selection of the largest ratios and the
+# generalised-Pareto fit run on the GPU (csrc/sr_loo.hip); there is no CPU fallback.
+_LOO_SCALARS = ("elpd", "se", "p_loo", "lppd_sum", "looic")
+_LOO_ARRAYS = {"elpd": "elpd_loo", "pareto_k": "pareto_k", "lppd": "lppd", "p_loo_cell": "p_loo_i"}
+
+
+def _loo_outs(N, M, pointwise):
+    arrs = {"site_elpd": np.zeros(N), "taxon_elpd": np.zeros(M)}
+    out = L.sr_loo_out()
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data_as(_DBLP))
+    if pointwise:
+        for k, field in _LOO_ARRAYS.items():
+            arrs[k] = np.zeros((N, M))
+            setattr(out, field, arrs[k].ctypes.data_as(_DBLP))
+    return out, arrs
+
+
+def _loo_result(out, arrs, total):
+    res = {k: getattr(out, k) for k in _LOO_SCALARS}
+    res["elpd_loo"] = res.pop("elpd")   # "elpd" names the pointwise array, as in a WAIC result
+    res["n_k"] = [int(v) for v in out.n_k]
+    res["tail_len"] = int(out.tail_len)
+    res["total"] = total
+    res["kernel_ms"] = out.kernel_ms
+    res.update(arrs)
+    return res
+
+
+def loo_from_records(dataset, ab_pi, cd, manycd=False, pointwise=True, device=0):
+    """sr_loo: ab_pi and cd as waic_from_records takes them (the rates in [-600, -2^-50]) -> {"elpd_loo", "se",
+    "p_loo", "lppd_sum", "looic" (floats), "n_k" (the cells with pareto_k <= 0.5, <= 0.7, <= 1 and above), "tail_len",
+    "site_elpd" [N], "taxon_elpd" [M], "total" (the number of samples), "kernel_ms"}; pointwise adds "elpd" (the
+    elpd_loo array: waic_compare reads it), "pareto_k", "lppd" and "p_loo_cell" = lppd - elpd, [N][M] each."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    r = np.ascontiguousarray(cd, dtype=np.float64)
+    assert r.shape == (n_sel, count, 2 * dataset.M if manycd else 3)
+    out, arrs = _loo_outs(dataset.N, dataset.M, pointwise)
+    _check(L.lib().sr_loo(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)),
+                          r.ctypes.data_as(_DBLP), int(bool(manycd)), n_sel, count, device, ctypes.byref(out)),
+           "sr_loo")
+    return _loo_result(out, arrs, n_sel * count)
+
+
+def loo_from_session(session, chains, first=0, count=None, pointwise=True):
+    """sr_session_loo: the same over a session's records and rates still in HBM, rows [first, first + count) of
+    chains (session chain indices in selection order); shared or per-taxon rates as the session samples them."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs = _loo_outs(session.ds.N, session.ds.M, pointwise)
+    _check(L.lib().sr_session_loo(session.h, ch, len(chains), first, count, ctypes.byref(out)), "sr_session_loo")
+    return _loo_result(out, arrs, len(chains) * count)
 
 
 # ---------------------------------------------------------------- posterior predictive checks
