@@ -546,6 +546,48 @@ int sr_ppc(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t
 int sr_session_ppc(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count, uint64_t seed,
                    int32_t reps, sr_ppc_out *out);
 
+/* ---- cell occupancy and the per-site, per-taxon error tallies over saved samples: exact counts ----
+ * (an extension.  sr_posterior's alive, false_alive and false_ones reproduce the reference script's three occupancy
+ * plots with their quirks -- the site's row index in place of its sampled position, a closed interval, an accumulator
+ * that is never reset, a fixed divisor of 1000 -- so they are not the posterior probability that taxon m lived at
+ * site n; these counts are.)  Joint functions of (pi, a, b) and X, which no per-column output can give.
+ * Inputs: records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position, chains in selection order;
+ * T = n_sel * count samples; ds supplies N, M and X.  Cell (n, m) is alive in a sample when a_m <= pi_n < b_m,
+ * compared in int32: any int16 value is legal, nothing wraps and nothing is "outside".  No rates and no flip input:
+ * reflecting a chain (a' = N - b, b' = N - a, pi' = N - 1 - pi) changes no alive bit and therefore no output.
+ * Per sample, with x = X[n][m] (non-zero counts as 1):
+ *   for site n over the M taxa    alive_n  the taxa alive at the site
+ *                                 f0_n     the taxa alive with x = 0 (false zeros, Lazarus gaps)
+ *                                 f1_n     the taxa not alive with x = 1 (false ones)
+ *   for taxon m over the N sites  alive_m, f0_m, f1_m likewise
+ * Outputs, unsigned counts over the T samples; every pointer is optional (NULL = skip), a call only pays for what
+ * it asks, and one that asks for nothing succeeds:
+ *   alive [N][M]                                             the samples in which cell (n, m) is alive
+ *   site_alive_hist, site_f0_hist, site_f1_hist [N][M+1]     entry [n][r]: the samples with alive_n (f0_n, f1_n) equal
+ *                                                            to r; every row sums to T
+ *   taxon_alive_hist, taxon_f0_hist, taxon_f1_hist [M][N+1]  the same per taxon; every row sums to T
+ * (taxon_alive_hist is not sr_relations' dur_hist in general: it counts the sites inside the range, which equals
+ * b - a when pi is a permutation of 0..N-1 and 0 <= a <= b <= N.)  kernel_ms, the kernels' time, is always written.
+ * The results do not depend on the order of the adds.  No device scratch beyond the outputs and X is allocated.
+ * SR_EINVAL: NULL ds, ab_pi or out, n_sel <= 0, count < 1, n_sel * count >= 2^31, N outside 1..32767, M < 1; the
+ * session form also for rows beyond the buffered records or a chain index out of range.  SR_EUNSUPPORTED: N M > 2^27,
+ * a requested histogram larger than 1 GiB (N (M+1) or M (N+1) > 2^28), or a library built without the device layer.
+ * All reported before any device call, the outputs untouched. */
+typedef struct {
+  uint32_t *alive;                                             /* out: [N][M], NULL = skip */
+  uint32_t *site_alive_hist, *site_f0_hist, *site_f1_hist;     /* out: [N][M+1] each, NULL = skip */
+  uint32_t *taxon_alive_hist, *taxon_f0_hist, *taxon_f1_hist;  /* out: [M][N+1] each, NULL = skip */
+  double kernel_ms;                                            /* out */
+} sr_occ_out;
+
+/* records in host memory: ab_pi [n_sel][count][2M+N] int16; ds supplies N, M and X */
+int sr_occupancy(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                 sr_occ_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order), on the session's
+   stream; the session's state and records are left untouched */
+int sr_session_occupancy(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                         sr_occ_out *out);
+
 /* ---- chain agreement: pairwise order distances between chains and mode clustering: exact integers ----
  * (an extension: the reference's choose_chains ranks chains by mean -loglik and never asks whether they sampled the
  * same order.)  Records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position; only the pi part is

@@ -1052,7 +1052,7 @@ static double *post_slot(sr_posterior_out *o, int k)
 
 /* ---- the record view of the analyses below (sr_records.h) ---- */
 /* The view's functions (sr_records.hip) and the analyses' entry points (sr_post, sr_diag, sr_marg, sr_rel, sr_agree,
-   sr_waic, sr_loo, sr_central, sr_ppc .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
+   sr_waic, sr_loo, sr_central, sr_ppc, sr_occ .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
    every analysis reports SR_EUNSUPPORTED, after its argument checks and before anything is uploaded. */
 #define SR_WEAK(f) extern __typeof__(f) f __attribute__((weak))
 SR_WEAK(sr_recview_host);
@@ -1069,6 +1069,7 @@ SR_WEAK(srl_loo);
 SR_WEAK(src_central);
 SR_WEAK(src_order_loss);
 SR_WEAK(srq_ppc);
+SR_WEAK(sro_occupancy);
 
 /* the device layer's return code (0, -1, -4, anything else) as an SR_* code */
 static int sr_code_of(int rc) { return rc == 0 ? SR_OK : (rc == -1 ? SR_EINVAL : (rc == -4 ? SR_ENOMEM : SR_EDEVICE)); }
@@ -2061,6 +2062,64 @@ SR_API int sr_session_ppc(sr_session *s, const int32_t *chains, int32_t n_sel, i
   sr_recview_release(&v);
   free(rows);
   free(buf);
+  return rc;
+}
+
+/* ---- cell occupancy and the site and taxon error tallies: exact counts (definitions: include/seriation.h) ---- */
+/* the argument checks both forms share, made before any device call */
+static int occ_check(const sr_occ_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M)
+{
+  if (!out || n_sel <= 0 || count < 1 || (int64_t)n_sel * count >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  if ((int64_t)N * M > WAIC_CELLS_MAX) return SR_EUNSUPPORTED;
+  if ((out->site_alive_hist || out->site_f0_hist || out->site_f1_hist) && (int64_t)N * ((int64_t)M + 1) > REL_OUT_MAX)
+    return SR_EUNSUPPORTED;
+  if ((out->taxon_alive_hist || out->taxon_f0_hist || out->taxon_f1_hist) && (int64_t)M * (N + 1) > REL_OUT_MAX)
+    return SR_EUNSUPPORTED;
+  return SR_OK;
+}
+
+static int occ_run(const sr_recview *v, const sr_dataset *ds, sr_occ_out *out)
+{
+  uint32_t *const site[3] = {out->site_alive_hist, out->site_f0_hist, out->site_f1_hist};
+  uint32_t *const taxon[3] = {out->taxon_alive_hist, out->taxon_f0_hist, out->taxon_f1_hist};
+  float ms = 0.0f;
+  const int rc = sro_occupancy(v, ds->N, ds->M, ds->X, out->alive, site, taxon, &ms);
+  out->kernel_ms = ms;
+  return sr_code_of(rc);
+}
+
+SR_API int sr_occupancy(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int32_t count, int32_t device,
+                        sr_occ_out *out)
+{
+  if (!ds || !ab_pi) return SR_EINVAL;
+  int rc = occ_check(out, n_sel, count, ds->N, ds->M);
+  if (rc) return rc;
+  if (!ds->X) return SR_EINVAL;
+  if (!sro_occupancy) return SR_EUNSUPPORTED;
+  if (!out->alive && !out->site_alive_hist && !out->site_f0_hist && !out->site_f1_hist && !out->taxon_alive_hist &&
+      !out->taxon_f0_hist && !out->taxon_f1_hist) {   /* nothing asked for: nothing is uploaded */
+    out->kernel_ms = 0.0;
+    return SR_OK;
+  }
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = occ_run(&v, ds, out);
+  sr_recview_release(&v);
+  return rc;
+}
+
+SR_API int sr_session_occupancy(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                sr_occ_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = occ_check(out, n_sel, count, s->ds.N, s->ds.M);
+  if (rc == SR_EINVAL) return rc;
+  sr_recview v;   /* an invalid selection wins over an output too large */
+  rc = session_view(s, chains, n_sel, first, count, rc ? rc : (sro_occupancy ? SR_OK : SR_EUNSUPPORTED), &v);
+  if (rc) return rc;
+  rc = occ_run(&v, &s->ds, out);
+  sr_recview_release(&v);
   return rc;
 }
 

@@ -1,6 +1,7 @@
 /*
  * sr_records.h -- the record view: how the analyses over saved records (posterior summaries, convergence
- * diagnostics, marginals, taxon-pair relations, WAIC, PSIS-LOO, chain agreement, the central state, posterior predictive checks)
+ * diagnostics, marginals, taxon-pair relations, WAIC, PSIS-LOO, chain agreement, the central state, posterior predictive checks,
+ * cell occupancy)
  * address the rows they read, and those
  * analyses' entry points.  Plain C.  Included by sr_host.c, sr_records.hip and the analysis .hip files only: the
  * sweep kernel's sources (sr_device.hip, sr_internal.h; the snapshot sr_spec.c compiles from) know nothing of it.
@@ -112,6 +113,12 @@ int srq_ppc(const sr_recview *v, int N, int M, const uint8_t *X, const double *c
             uint64_t seed, int reps, uint32_t *taxon_gt, uint32_t *taxon_eq, long long *taxon_sum_obs,
             long long *taxon_sum_rep, uint32_t *site_gt, uint32_t *site_eq, long long *site_sum_rep,
             long long *total_obs, long long *total_rep, long long *total_gt, long long *total_eq, float *ms);
+
+/* cell occupancy and the site and taxon error tallies (sr_occ.hip): exact counts, defined in include/seriation.h.
+   X [N][M] is an input; alive [N][M], site[3] (the histograms of alive, f0, f1: [N][M+1] each) and taxon[3]
+   ([M][N+1] each) are outputs, each optional (the two arrays of three pointers themselves are not) */
+int sro_occupancy(const sr_recview *v, int N, int M, const uint8_t *X, uint32_t *alive, uint32_t *const site[3],
+                  uint32_t *const taxon[3], float *ms);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                                     [--seed-base S] [--devices 0,1] [--root .] [--select K]
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
                                     [--marginals] [--relations] [--waic] [--loo] [--modes [--mode-threshold X]]
-                                    [--central] [--ppc [--ppc-seed S] [--ppc-reps R]]
+                                    [--central] [--ppc [--ppc-seed S] [--ppc-reps R]] [--occupancy]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -41,6 +41,14 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 the mean total of the data and of the replicates, the p-value (gt + eq / 2) / pairs and its counts;
                 Chains/ppc_taxa.csv: the same means and p per taxon and discrepancy; Chains/ppc_sites.csv: per site
                 its number of taxa in the data, the replicates' mean and p
+  --occupancy   with --select: cell occupancy and the error tallies of the chosen chains (analysis.occupancy_from_records
+                over their chain_data.csv; no orientation pass: nothing depends on the flips).  A taxon is alive at a
+                site in a sample when the site's sampled position lies inside the taxon's sampled range.
+                Chains/occupancy_cells.csv: site, taxon, x, alive (the samples in which the cell is alive), p_alive;
+                Chains/occupancy_sites.csv: per site the row sum of X, the mean and the 2.5 %, 50 % and 97.5 %
+                quantiles of the taxa alive, of the false zeros (alive, x = 0) and of the false ones (not alive,
+                x = 1), and the completeness (the expected share of the taxa alive at the site that were found);
+                Chains/occupancy_taxa.csv: the same per taxon over the sites, without the completeness
   --modes       which chains sampled the same order, over all chains of the run, before and independent of --select
                 (analysis.agreement_from_records and chain_modes over their chain_data.csv).  Chains/chain_modes.csv:
                 per chain its mode, its flip against the mode's first chain, whether it is the mode's medoid, the
@@ -113,6 +121,41 @@ def write_relations(ds, chains, root, device=0):
             for j in range(i + 1, ds.M):
                 fh.write("%d,%d,%d,%d,%d,%d,%d,%d,%d\n" % (i, j, ob[i][j], ob[j][i], eb[i][j], eb[j][i], pr[i][j],
                                                           pr[j][i], ov[i][j]))
+
+
+def write_occupancy(ds, chains, root, device=0):
+    """Chains/occupancy_cells.csv, Chains/occupancy_sites.csv and Chains/occupancy_taxa.csv of the chosen chains: the
+    exact occupancy counts over their chain_data.csv rows."""
+    import numpy as np
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    r = analysis.occupancy_from_records(ds, rec, device=device)
+    X = np.ctypeslib.as_array(ds.c.X, (ds.N * ds.M,)).reshape(ds.N, ds.M).astype(bool)
+    alive, p = r["alive"].tolist(), r["p_alive"].tolist()
+    with open(os.path.join(root, "Chains", "occupancy_cells.csv"), "w") as fh:
+        fh.write("site,taxon,x,alive,p_alive\n")
+        for n in range(ds.N):
+            for m in range(ds.M):
+                fh.write("%d,%d,%d,%d,%r\n" % (n, m, X[n, m], alive[n][m], p[n][m]))
+    cols = ",".join("%s_mean,%s" % (k, ",".join("%s_q%s" % (k, q) for q in analysis.PROBS))
+                    for k in ("alive", "f0", "f1"))
+
+    def bands(prefix, j):
+        out = []
+        for k in ("alive", "f0", "f1"):
+            dc = curves[prefix + k]
+            out.append("%r,%s" % (float(dc["mean"][j]), ",".join(str(q) for q in dc["quant"][:, j])))
+        return ",".join(out)
+
+    curves = {k[:-5]: analysis.diversity_curve(r[k], analysis.PROBS) for k in analysis.OCC_KINDS if k != "alive"}
+    with open(os.path.join(root, "Chains", "occupancy_sites.csv"), "w") as fh:
+        fh.write("site,x_sum,%s,completeness\n" % cols)
+        for n in range(ds.N):
+            fh.write("%d,%d,%s,%r\n" % (n, X[n].sum(), bands("site_", n), float(r["site_completeness"][n])))
+    with open(os.path.join(root, "Chains", "occupancy_taxa.csv"), "w") as fh:
+        fh.write("taxon,x_sum,%s\n" % cols)
+        for m in range(ds.M):
+            fh.write("%d,%d,%s\n" % (m, X[:, m].sum(), bands("taxon_", m)))
 
 
 def write_ppc(ds, chains, root, manycd=False, seed=0, reps=1, device=0):
@@ -263,6 +306,7 @@ def main(argv=None):
     ap.add_argument("--ppc", action="store_true")
     ap.add_argument("--ppc-seed", type=int, default=0)
     ap.add_argument("--ppc-reps", type=int, default=1)
+    ap.add_argument("--occupancy", action="store_true")
     ap.add_argument("--modes", action="store_true")
     ap.add_argument("--mode-threshold", type=float, default=0.1)
     ap.add_argument("--central", action="store_true")
@@ -279,6 +323,8 @@ def main(argv=None):
         ap.error("--ppc needs --select K (and the chain files: not with --no-save)")
     if a.ppc and not (1 <= a.ppc_reps <= 64 and 0 <= a.ppc_seed < 2 ** 64):
         ap.error("--ppc-reps must lie in 1..64 and --ppc-seed in 0..2^64-1")
+    if a.occupancy and (a.select < 1 or a.no_save):
+        ap.error("--occupancy needs --select K (and the chain files: not with --no-save)")
     if a.marginals and (a.select < 1 or a.no_save):
         ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
     if a.relations and (a.select < 1 or a.no_save):
@@ -329,6 +375,8 @@ def main(argv=None):
             if a.ppc:
                 write_ppc(core.Dataset.load(a.dataset), chosen, a.root, a.manycd, a.ppc_seed, a.ppc_reps,
                           devices[0] if devices else 0)
+            if a.occupancy:
+                write_occupancy(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
             if a.central:
                 print("central: chain %d row %d" % write_central(core.Dataset.load(a.dataset), chosen, a.root,
                                                                   devices[0] if devices else 0))

@@ -614,6 +614,82 @@ def ppc_from_session(session, chains, first=0, count=None, seed=0, reps=1, total
     return _ppc_result(out, arrs)
 
 
+# ---------------------------------------------------------------- cell occupancy and the error tallies
+# Was taxon m alive at site n, which absences are Lazarus gaps and which occurrences lie outside the taxon's range,
+# which sites and which taxa carry the errors: joint functions of (pi, a, b) and X, counted exactly over the selected
+# chains' samples (definitions: include/seriation.h).  The counts come from the GPU (csrc/sr_occ.hip); there is no CPU
+# fallback.  No orientation is needed: a reflected chain gives the same alive bits.  Means and quantile bands of the
+# six histograms: diversity_curve.
+OCC_KINDS = ("alive", "site_alive_hist", "site_f0_hist", "site_f1_hist", "taxon_alive_hist", "taxon_f0_hist",
+             "taxon_f1_hist")
+
+
+def _occ_outs(N, M, kinds):
+    shapes = {k: ((N, M) if k == "alive" else (N, M + 1) if k.startswith("site_") else (M, N + 1)) for k in OCC_KINDS}
+    arrs = {k: np.zeros(shapes[k], np.uint32) for k in kinds}
+    out = L.sr_occ_out()
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    return out, arrs
+
+
+def occupancy_derived(alive, X, total):
+    """alive [N][M] (exact counts over `total` samples) and X [N][M] -> the host-side f64 values, each one division of
+    exact integers: "p_alive" = alive / T; "p_false_zero" = alive / T where x = 0, NaN elsewhere; "p_false_one" =
+    (T - alive) / T where x = 1, NaN elsewhere; "site_completeness" [N] = sum_m x alive / sum_m alive, the expected
+    share of the taxa alive at the site that were found there (NaN when the denominator is 0)."""
+    a = np.asarray(alive).astype(np.int64)
+    x = np.asarray(X) != 0
+    T = np.float64(total)
+    p = a.astype(np.float64) / T
+    den = a.sum(axis=1)
+    num = np.where(x, a, 0).sum(axis=1)
+    comp = np.full(a.shape[0], np.nan)
+    np.divide(num.astype(np.float64), den.astype(np.float64), out=comp, where=den != 0)
+    return {"p_alive": p, "p_false_zero": np.where(x, np.nan, p),
+            "p_false_one": np.where(x, (np.int64(total) - a).astype(np.float64) / T, np.nan),
+            "site_completeness": comp}
+
+
+def _occ_result(out, arrs, X, total):
+    res = dict(arrs)
+    res["total"] = total
+    res["kernel_ms"] = out.kernel_ms
+    if "alive" in arrs:
+        res.update(occupancy_derived(arrs["alive"], X, total))
+    return res
+
+
+def _dataset_x(ds):
+    return np.ctypeslib.as_array(ds.c.X, (ds.N * ds.M,)).reshape(ds.N, ds.M).copy()
+
+
+def occupancy_from_records(dataset, ab_pi, kinds=OCC_KINDS, device=0):
+    """sr_occupancy: ab_pi [n_sel][count][2M+N] (a | b | pi rows, chains in selection order) -> {kind: uint32 array}
+    for the requested kinds ("alive": [N][M]; "site_alive_hist", "site_f0_hist", "site_f1_hist": [N][M+1];
+    "taxon_alive_hist", "taxon_f0_hist", "taxon_f1_hist": [M][N+1]) plus "total" (the number of samples T) and
+    "kernel_ms"; with "alive" also "p_alive", "p_false_zero", "p_false_one" [N][M] and "site_completeness" [N]
+    (occupancy_derived)."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    out, arrs = _occ_outs(dataset.N, dataset.M, kinds)
+    _check(L.lib().sr_occupancy(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)), n_sel,
+                                count, device, ctypes.byref(out)), "sr_occupancy")
+    return _occ_result(out, arrs, _dataset_x(dataset), n_sel * count)
+
+
+def occupancy_from_session(session, chains, first=0, count=None, kinds=OCC_KINDS):
+    """sr_session_occupancy: the same over a session's records still in HBM, rows [first, first + count) of chains
+    (session chain indices in selection order)."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    out, arrs = _occ_outs(session.ds.N, session.ds.M, kinds)
+    _check(L.lib().sr_session_occupancy(session.h, ch, len(chains), first, count, ctypes.byref(out)),
+           "sr_session_occupancy")
+    return _occ_result(out, arrs, _dataset_x(session.ds), len(chains) * count)
+
+
 # ---------------------------------------------------------------- chain agreement and modes
 # Which chains sampled the same order: per chain the exact counts of every site pair's order, the L1 distance between
 # every two chains' counts, plain and against the mirror image, and the single-linkage modes read off them
