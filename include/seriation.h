@@ -588,6 +588,65 @@ int sr_occupancy(const sr_dataset *ds, const int16_t *ab_pi, int32_t n_sel, int3
 int sr_session_occupancy(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
                          sr_occ_out *out);
 
+/* ---- Placement: where a row that was not in the run belongs in the seriation, every output defined to the bit ----
+ * (an extension.)  A new or fragmentary locality comes as a faunal list; given a sample's ranges and rates its
+ * likelihood at a position is a product over the taxa, and the posterior placement is the average over the samples
+ * of that likelihood normalised over the positions.  Position p means "of the same age as whichever site sits at
+ * position p" (co-location, not insertion between two sites); placing one of the run's own rows is in-sample.
+ * Inputs: records, ds (N, M; X is not read), cd, manycd, n_sel, count exactly as sr_waic takes them: rows
+ * [a (M) | b (M) | pi (N)] int16, chains in selection order, the rates on the log scale, every c and d that is read
+ * in [-700, -2^-50]; T = n_sel * count samples (one is enough).  Y [Q][M] uint8: 0 absent, 1 present, 2 not assessed.
+ * flip [n_sel] or NULL: a flagged chain's rows are reflected first, in int32, as sr_marginals reflects them:
+ * a' = N - b, b' = N - a, pi' = N - 1 - pi; everything below is defined on the reflected rows.
+ * Term table, per sample (and per taxon when manycd), WAIC's l[4] = {log(1.0 - exp(c)), d, log(1.0 - exp(d)), c}
+ * with this library's exp and log (bit for bit the C library's).
+ * Profile of sample (k, r), query q, candidate position p in 0..N-1: L[p] = the sequential sum from +0.0, over m
+ * ascending, of l[idx] of taxon m, idx WAIC's index with alive = a_m <= p < b_m (compared in int32: any int16 is
+ * legal) and y = Y[q][m]: 0 for (y = 0, not alive), 1 for (y = 0, alive), 2 for (y = 1, alive), 3 for (y = 1, not
+ * alive).  A cell with y = 2 contributes +0.0, which equals skipping it (no partial sum is ever -0.0: each starts at
+ * +0.0 and every term is <= +0.0).
+ * Normalisation: mx = max_p L[p]; e[p] = exp(L[p] - mx) over the whole domain of exp (subnormal results and
+ * underflow to 0.0 are legal and are the C library's); z_j, j in 0..63, the sequential sum from +0.0 of e[p] over
+ * p = j, j + 64, j + 128, ... < N; Z the sequential sum from +0.0 of z_0 ... z_63, j ascending (Z >= 1 always);
+ * w[p] = e[p] / Z; lse = mx + log(Z).
+ * Accumulation, in WAIC's order: within chain k sequentially over r ascending from +0.0, then the chain sums
+ * sequentially over k ascending from +0.0; no fma outside exp and log, no floating-point atomic:
+ *   Spos[q][p] += w[p];   Ssite[q][n] += (0 <= pi'_n < N ? w[pi'_n] : +0.0).
+ * Outputs; every array is optional (NULL = skip), and a call that asks for nothing succeeds:
+ *   pos  [Q][N] = Spos / (double)T      the posterior probability that query q is of the age of position p
+ *   site [Q][N] = Ssite / (double)T     ... of the age of site n; reflecting a chain moves each e to the mirrored
+ *                                       position, so site depends on the flags only through the rounding of Z
+ *   lse  [n_sel][count][Q]              each sample's log of the sum over positions of the query's likelihood
+ *   lpd  [Q], in plain C on the host after the kernels: mxx the maximum of the query's lse, s the sequential sum
+ *        from +0.0 over (k major, r) of exp(lse - mxx), lpd = mxx + log(s / (double)T) - log((double)N): the log
+ *        predictive density of the query row under a uniform prior over the positions, comparable between queries
+ *        with the same assessed taxa
+ *   kernel_ms, the kernels' time, is always written.
+ * Device scratch is bounded as WAIC's is: chains and rows are taken in batches of at most SR_PLACE_SCRATCH bytes
+ * (read from the environment at each call, 256 MiB by default, one chain and one row at the least); the results do
+ * not depend on it.
+ * SR_EINVAL: NULL ds, ds->X, ab_pi, cd, Y or out, Q < 1, a Y value above 2, T < 1 or T >= 2^31, N outside 1..32767,
+ * M < 1, a rate outside the domain or NaN; the session form also for rows beyond the buffered records or a chain
+ * index out of range.  SR_EUNSUPPORTED: Q N > 2^27, or a library built without the device layer.  All reported
+ * before the device is touched, the outputs untouched. */
+typedef struct {
+  const uint8_t *flip;   /* in: [n_sel], non-zero = reflect that chain's rows first; NULL = none */
+  double *pos;           /* out: [Q][N], NULL = skip */
+  double *site;          /* out: [Q][N], NULL = skip */
+  double *lse;           /* out: [n_sel][count][Q], NULL = skip */
+  double *lpd;           /* out: [Q], NULL = skip */
+  double kernel_ms;      /* out */
+} sr_place_out;
+
+/* records and rates in host memory, as sr_waic takes them; Y [Q][M] */
+int sr_placement(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel,
+                 int32_t count, const uint8_t *Y, int32_t Q, int32_t device, sr_place_out *out);
+/* the session's own records in HBM, rows [first, first+count) of chains[] (selection order), shared or per-taxon
+   rates as the session samples them (fetched as sr_session_waic fetches them); the session's state and records are
+   left untouched */
+int sr_session_placement(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                         const uint8_t *Y, int32_t Q, sr_place_out *out);
+
 /* ---- chain agreement: pairwise order distances between chains and mode clustering: exact integers ----
  * (an extension: the reference's choose_chains ranks chains by mean -loglik and never asks whether they sampled the
  * same order.)  Records are rows [a (M) | b (M) | pi (N)] int16 as above, pi[site] = position; only the pi part is

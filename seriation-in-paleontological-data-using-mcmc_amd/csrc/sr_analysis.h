@@ -1,7 +1,7 @@
 /*
  * sr_analysis.h -- what the host code of the analysis units shares.  HIP only: included by sr_records.hip and the
- * ten analysis .hip files (sr_post, sr_diag, sr_marg, sr_rel, sr_waic, sr_loo, sr_agree, sr_central, sr_ppc, sr_occ), by nothing
- * else.
+ * eleven analysis .hip files (sr_post, sr_diag, sr_marg, sr_rel, sr_waic, sr_loo, sr_agree, sr_central, sr_ppc, sr_occ,
+ * sr_place), by nothing else.
  */
 #ifndef SR_ANALYSIS_H
 #define SR_ANALYSIS_H

@@ -1052,7 +1052,7 @@ static double *post_slot(sr_posterior_out *o, int k)
 
 /* ---- the record view of the analyses below (sr_records.h) ---- */
 /* The view's functions (sr_records.hip) and the analyses' entry points (sr_post, sr_diag, sr_marg, sr_rel, sr_agree,
-   sr_waic, sr_loo, sr_central, sr_ppc, sr_occ .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
+   sr_waic, sr_loo, sr_central, sr_ppc, sr_occ, sr_place .hip) are absent from the host-only builds, whose device layer is a stub: weak, so those builds link and
    every analysis reports SR_EUNSUPPORTED, after its argument checks and before anything is uploaded. */
 #define SR_WEAK(f) extern __typeof__(f) f __attribute__((weak))
 SR_WEAK(sr_recview_host);
@@ -1070,6 +1070,7 @@ SR_WEAK(src_central);
 SR_WEAK(src_order_loss);
 SR_WEAK(srq_ppc);
 SR_WEAK(sro_occupancy);
+SR_WEAK(srx_place);
 
 /* the device layer's return code (0, -1, -4, anything else) as an SR_* code */
 static int sr_code_of(int rc) { return rc == 0 ? SR_OK : (rc == -1 ? SR_EINVAL : (rc == -4 ? SR_ENOMEM : SR_EDEVICE)); }
@@ -2120,6 +2121,98 @@ SR_API int sr_session_occupancy(sr_session *s, const int32_t *chains, int32_t n_
   if (rc) return rc;
   rc = occ_run(&v, &s->ds, out);
   sr_recview_release(&v);
+  return rc;
+}
+
+/* ---- placement of query rows in the seriation (definitions: include/seriation.h "Placement") ---- */
+#define PLACE_OUT_MAX ((int64_t)1 << 27)
+
+/* the argument checks both forms share, made before any device call */
+static int place_check(const sr_place_out *out, int32_t n_sel, int32_t count, int32_t N, int32_t M, const uint8_t *Y,
+                       int32_t Q)
+{
+  if (!out || !Y || Q < 1 || n_sel <= 0 || count < 1 || (int64_t)n_sel * count >= ((int64_t)1 << 31)) return SR_EINVAL;
+  if (N < 1 || N > 32767 || M < 1) return SR_EINVAL;
+  for (int64_t i = 0; i < (int64_t)Q * M; i++)
+    if (Y[i] > 2) return SR_EINVAL;
+  return SR_OK;
+}
+
+/* lpd on the host from the samples' lse; lse is a temporary here when the caller asked for lpd alone */
+static int place_run(const sr_recview *v, const sr_dataset *ds, sr_place_out *out, const double *const *cd, int cdw,
+                     int manycd, const uint8_t *Y, int32_t Q)
+{
+  const int64_t T = (int64_t)v->n_sel * v->count;
+  out->kernel_ms = 0.0;
+  if (!out->pos && !out->site && !out->lse && !out->lpd) return SR_OK;   /* nothing asked for */
+  double *lse = out->lse;
+  if (!lse && out->lpd) {
+    lse = (double *)malloc(sizeof(double) * (size_t)T * Q);
+    if (!lse) return SR_ENOMEM;
+  }
+  float ms = 0.0f;
+  int rc = sr_code_of(srx_place(v, ds->N, ds->M, cd, cdw, manycd, Y, Q, out->flip, out->pos, out->site, lse, &ms));
+  if (!rc) out->kernel_ms = ms;
+  if (!rc && out->lpd)
+    for (int32_t q = 0; q < Q; q++) {
+      double mxx = lse[q], s = 0.0;
+      for (int64_t t = 1; t < T; t++)
+        if (lse[t * Q + q] > mxx) mxx = lse[t * Q + q];
+      for (int64_t t = 0; t < T; t++) s += h_exp(lse[t * Q + q] - mxx);
+      out->lpd[q] = mxx + h_log(s / (double)T) - h_log((double)ds->N);
+    }
+  if (lse != out->lse) free(lse);
+  return rc;
+}
+
+SR_API int sr_placement(const sr_dataset *ds, const int16_t *ab_pi, const double *cd, int32_t manycd, int32_t n_sel,
+                        int32_t count, const uint8_t *Y, int32_t Q, int32_t device, sr_place_out *out)
+{
+  if (!ds || !ab_pi || !cd) return SR_EINVAL;
+  int rc = place_check(out, n_sel, count, ds->N, ds->M, Y, Q);
+  if (rc) return rc;
+  if (!ds->X) return SR_EINVAL;
+  const int Mt = manycd ? ds->M : 1, cdw = manycd ? 2 * ds->M : 3;
+  if (!waic_cd_ok(cd, (int32_t)((int64_t)n_sel * count), cdw, Mt)) return SR_EINVAL;
+  if ((int64_t)Q * ds->N > PLACE_OUT_MAX) return SR_EUNSUPPORTED;
+  if (!srx_place) return SR_EUNSUPPORTED;
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  if (!rows) return SR_ENOMEM;
+  for (int k = 0; k < n_sel; k++) rows[k] = cd + (size_t)k * count * cdw;
+  sr_recview v;
+  rc = sr_code_of(sr_recview_host(&v, device, ab_pi, n_sel, count, 2LL * ds->M + ds->N));
+  if (!rc) rc = place_run(&v, ds, out, rows, cdw, manycd != 0, Y, Q);
+  sr_recview_release(&v);
+  free(rows);
+  return rc;
+}
+
+SR_API int sr_session_placement(sr_session *s, const int32_t *chains, int32_t n_sel, int32_t first, int32_t count,
+                                const uint8_t *Y, int32_t Q, sr_place_out *out)
+{
+  if (!s || !chains) return SR_EINVAL;
+  int rc = place_check(out, n_sel, count, s->ds.N, s->ds.M, Y, Q);
+  if (rc) return rc;
+  sr_recview v;
+  rc = session_view(s, chains, n_sel, first, count,
+                    (int64_t)Q * s->ds.N > PLACE_OUT_MAX || !srx_place ? SR_EUNSUPPORTED : SR_OK, &v);
+  if (rc) return rc;
+  const int M = s->ds.M, manycd = s->opts.manycd != 0;
+  const int Mt = manycd ? M : 1, cdw = manycd ? 2 * M : 3;
+  /* the rates come to the host as sr_session_waic fetches them */
+  const double **rows = (const double **)malloc(sizeof(double *) * n_sel);
+  double *buf = (double *)malloc(sizeof(double) * (size_t)(manycd ? s->nchains : n_sel) * count * cdw);
+  rc = (rows && buf) ? SR_OK : SR_ENOMEM;
+  if (!rc && manycd && srk_fetch_cdv(s->dev, first, count, buf)) rc = SR_EDEVICE;
+  for (int k = 0; k < n_sel && !rc; k++) {
+    rows[k] = buf + (size_t)(manycd ? chains[k] : k) * count * cdw;
+    if (!manycd && srk_fetch_chain_records(s->dev, chains[k], first, count, NULL, (double *)rows[k])) rc = SR_EDEVICE;
+    if (!rc && !waic_cd_ok(rows[k], count, cdw, Mt)) rc = SR_EINVAL;
+  }
+  if (!rc) rc = place_run(&v, &s->ds, out, rows, cdw, manycd, Y, Q);
+  sr_recview_release(&v);
+  free(rows);
+  free(buf);
   return rc;
 }
 

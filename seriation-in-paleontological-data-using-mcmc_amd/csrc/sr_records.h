@@ -1,7 +1,7 @@
 /*
  * sr_records.h -- the record view: how the analyses over saved records (posterior summaries, convergence
  * diagnostics, marginals, taxon-pair relations, WAIC, PSIS-LOO, chain agreement, the central state, posterior predictive checks,
- * cell occupancy)
+ * cell occupancy, placement of query rows)
  * address the rows they read, and those
  * analyses' entry points.  Plain C.  Included by sr_host.c, sr_records.hip and the analysis .hip files only: the
  * sweep kernel's sources (sr_device.hip, sr_internal.h; the snapshot sr_spec.c compiles from) know nothing of it.
@@ -119,6 +119,12 @@ int srq_ppc(const sr_recview *v, int N, int M, const uint8_t *X, const double *c
    ([M][N+1] each) are outputs, each optional (the two arrays of three pointers themselves are not) */
 int sro_occupancy(const sr_recview *v, int N, int M, const uint8_t *X, uint32_t *alive, uint32_t *const site[3],
                   uint32_t *const taxon[3], float *ms);
+
+/* placement of query rows (sr_place.hip): defined to the bit in include/seriation.h.  cd, cdw and manycd as srw_waic
+   takes them; Y [Q][M] (0 absent, 1 present, 2 not assessed) and flip [n_sel] (or NULL) are inputs; pos, site [Q][N]
+   and lse [n_sel][count][Q] outputs, each optional */
+int srx_place(const sr_recview *v, int N, int M, const double *const *cd, int cdw, int manycd, const uint8_t *Y, int Q,
+              const uint8_t *flip, double *pos, double *site, double *lse, float *ms);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                                     [--no-save] [--debug-check] [--rng mt|philox] [--manycd]
                                     [--marginals] [--relations] [--waic] [--loo] [--modes [--mode-threshold X]]
                                     [--central] [--ppc [--ppc-seed S] [--ppc-reps R]] [--occupancy]
+                                    [--place FILE]
 
   --thin        sweeps per saved sample (the reference's mcmc_sample runs 10, mcmc.c:225)
   --seed-base   chain k gets seed S + k; omitted -> unique 1-byte urandom seeds like
@@ -49,6 +50,14 @@ whole job at once and writes the same ``Chains/chain_NN`` tree:
                 quantiles of the taxa alive, of the false zeros (alive, x = 0) and of the false ones (not alive,
                 x = 1), and the completeness (the expected share of the taxa alive at the site that were found);
                 Chains/occupancy_taxa.csv: the same per taxon over the sites, without the completeness
+  --place FILE  with --select: where the rows of FILE belong in the seriation (analysis.placement_from_records over the
+                chosen chains' chain_data.csv, mirrored chains oriented first, shared rates or, with --manycd,
+                per-taxon rates).  FILE is in the dataset's format: a header `Q M`, then Q rows of M tokens 0, 1 or ?
+                (not assessed).  A position means "of the same age as whichever site sits there", not an insertion
+                between two sites.  Chains/placement.csv: per query its log predictive density, the mean, the mode and
+                the 2.5 %, 50 % and 97.5 % quantiles of its position, the run's site it most probably shares its age
+                with and that probability; Chains/placement_positions.csv: query, position, p;
+                Chains/placement_sites.csv: query, site, p
   --modes       which chains sampled the same order, over all chains of the run, before and independent of --select
                 (analysis.agreement_from_records and chain_modes over their chain_data.csv).  Chains/chain_modes.csv:
                 per chain its mode, its flip against the mode's first chain, whether it is the mode's medoid, the
@@ -156,6 +165,32 @@ def write_occupancy(ds, chains, root, device=0):
         fh.write("taxon,x_sum,%s\n" % cols)
         for m in range(ds.M):
             fh.write("%d,%d,%s\n" % (m, X[:, m].sum(), bands("taxon_", m)))
+
+
+def write_placement(ds, chains, root, queries, manycd=False, device=0):
+    """Chains/placement.csv, Chains/placement_positions.csv and Chains/placement_sites.csv of the chosen chains: the
+    placement of the query rows [Q][M] over their chain_data.csv rows, oriented against the first chain, the rates
+    read back from the files' c and d tokens."""
+    from . import analysis
+    rec = analysis.read_chain_rows(root, chains, ds.N, ds.M)
+    cd = analysis.read_chain_cd(root, chains, ds.M, manycd=manycd)
+    r = analysis.placement_from_records(ds, rec, cd, queries, manycd=manycd, flips=_oriented(ds, rec, device),
+                                        device=device)
+    s = analysis.placement_summary(r["pos"], r["site"], analysis.PROBS)
+    Q = r["pos"].shape[0]
+    with open(os.path.join(root, "Chains", "placement.csv"), "w") as fh:
+        fh.write("query,lpd,mean,mode,%s,best_site,p_best_site\n" % ",".join("q%s" % p for p in analysis.PROBS))
+        for q in range(Q):
+            fh.write("%d,%r,%r,%d,%s,%d,%r\n" % (q, float(r["lpd"][q]), float(s["mean"][q]), s["mode"][q],
+                                                 ",".join(str(v) for v in s["quant"][:, q]), s["best_site"][q],
+                                                 float(s["p_best_site"][q])))
+    for name, key, col in (("placement_positions.csv", "pos", "position"), ("placement_sites.csv", "site", "site")):
+        v = r[key].tolist()
+        with open(os.path.join(root, "Chains", name), "w") as fh:
+            fh.write("query,%s,p\n" % col)
+            for q in range(Q):
+                for j in range(ds.N):
+                    fh.write("%d,%d,%r\n" % (q, j, v[q][j]))
 
 
 def write_ppc(ds, chains, root, manycd=False, seed=0, reps=1, device=0):
@@ -307,6 +342,7 @@ def main(argv=None):
     ap.add_argument("--ppc-seed", type=int, default=0)
     ap.add_argument("--ppc-reps", type=int, default=1)
     ap.add_argument("--occupancy", action="store_true")
+    ap.add_argument("--place", default=None, metavar="FILE")
     ap.add_argument("--modes", action="store_true")
     ap.add_argument("--mode-threshold", type=float, default=0.1)
     ap.add_argument("--central", action="store_true")
@@ -325,6 +361,8 @@ def main(argv=None):
         ap.error("--ppc-reps must lie in 1..64 and --ppc-seed in 0..2^64-1")
     if a.occupancy and (a.select < 1 or a.no_save):
         ap.error("--occupancy needs --select K (and the chain files: not with --no-save)")
+    if a.place and (a.select < 1 or a.no_save):
+        ap.error("--place needs --select K (and the chain files: not with --no-save)")
     if a.marginals and (a.select < 1 or a.no_save):
         ap.error("--marginals needs --select K (and the chain files: not with --no-save)")
     if a.relations and (a.select < 1 or a.no_save):
@@ -377,6 +415,11 @@ def main(argv=None):
                           devices[0] if devices else 0)
             if a.occupancy:
                 write_occupancy(core.Dataset.load(a.dataset), chosen, a.root, devices[0] if devices else 0)
+            if a.place:
+                ds = core.Dataset.load(a.dataset)
+                from . import analysis
+                write_placement(ds, chosen, a.root, analysis.read_queries(a.place, ds.M), a.manycd,
+                                devices[0] if devices else 0)
             if a.central:
                 print("central: chain %d row %d" % write_central(core.Dataset.load(a.dataset), chosen, a.root,
                                                                   devices[0] if devices else 0))

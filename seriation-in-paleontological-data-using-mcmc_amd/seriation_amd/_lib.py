@@ -143,6 +143,13 @@ class sr_occ_out(ctypes.Structure):
                 ("kernel_ms", ctypes.c_double)]
 
 
+class sr_place_out(ctypes.Structure):
+    _fields_ = [("flip", ctypes.POINTER(ctypes.c_uint8)),
+                ("pos", ctypes.POINTER(ctypes.c_double)), ("site", ctypes.POINTER(ctypes.c_double)),
+                ("lse", ctypes.POINTER(ctypes.c_double)), ("lpd", ctypes.POINTER(ctypes.c_double)),
+                ("kernel_ms", ctypes.c_double)]
+
+
 class sr_agree_out(ctypes.Structure):
     _fields_ = [("pair_counts", ctypes.POINTER(ctypes.c_uint32)),
                 ("dist", ctypes.POINTER(ctypes.c_int64)), ("dist_mirror", ctypes.POINTER(ctypes.c_int64)),
@@ -179,6 +186,7 @@ PUBLIC_SYMBOLS = [
     "sr_relations", "sr_session_relations", "sr_waic", "sr_session_waic", "sr_waic_reduce",
     "sr_loo", "sr_session_loo", "sr_loo_reduce", "sr_loo_tail", "sr_loo_tail_len",
     "sr_ppc", "sr_session_ppc", "sr_occupancy", "sr_session_occupancy",
+    "sr_placement", "sr_session_placement",
     "sr_agreement", "sr_session_agreement", "sr_agreement_distances", "sr_agreement_modes",
     "sr_central", "sr_session_central", "sr_order_loss",
     "sr_strerror", "sr_device_count", "sr_version",
@@ -261,6 +269,10 @@ def _lib():
         "sr_session_ppc": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, ctypes.c_uint64, c_i32, P(sr_ppc_out)]),
         "sr_occupancy": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_occ_out)]),
         "sr_session_occupancy": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_occ_out)]),
+        "sr_placement": (c_int, [P(sr_dataset), P(ctypes.c_int16), P(c_double), c_i32, c_i32, c_i32, P(ctypes.c_uint8),
+                                 c_i32, c_i32, P(sr_place_out)]),
+        "sr_session_placement": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(ctypes.c_uint8), c_i32,
+                                         P(sr_place_out)]),
         "sr_agreement": (c_int, [P(sr_dataset), P(ctypes.c_int16), c_i32, c_i32, c_i32, P(sr_agree_out)]),
         "sr_session_agreement": (c_int, [c_void_p, P(c_i32), c_i32, c_i32, c_i32, P(sr_agree_out)]),
         "sr_agreement_distances": (c_int, [c_i32, c_i32, P(ctypes.c_uint32), c_i32, P(ctypes.c_int64),

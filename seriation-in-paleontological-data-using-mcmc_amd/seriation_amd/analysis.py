@@ -690,6 +690,119 @@ def occupancy_from_session(session, chains, first=0, count=None, kinds=OCC_KINDS
     return _occ_result(out, arrs, _dataset_x(session.ds), len(chains) * count)
 
 
+# ---------------------------------------------------------------- placement of query rows
+# Where does a row that was not in the run belong: a new or fragmentary locality's faunal list (0 absent, 1 present,
+# 2 not assessed) against the selected chains' samples.  Per sample the row's likelihood at every position, normalised
+# over the positions; averaged over the samples, per position ("pos") and per site of the run ("site"), every output
+# defined to the bit (definitions: include/seriation.h "Placement").  Position p means "of the same age as whichever
+# site sits at position p", not an insertion between two sites; placing one of the run's own rows is in-sample.  The
+# T Q N M part runs on the GPU (csrc/sr_place.hip); there is no CPU fallback.  Orient the chains first (flips):
+# "pos" of mirrored chains averages a distribution with its mirror image.
+def _place_outs(N, n_sel, count, Q, flips, lse):
+    n, c, q = max(int(n_sel), 0), max(int(count), 0), max(int(Q), 0)
+    arrs = {"pos": np.zeros((q, N)), "site": np.zeros((q, N)), "lpd": np.zeros(q)}
+    if lse:
+        arrs["lse"] = np.zeros((n, c, q))
+    out = L.sr_place_out()
+    f, fp = _flip_arg(flips, n_sel)
+    if f is not None:
+        out.flip = fp
+    for k, a in arrs.items():
+        setattr(out, k, a.ctypes.data_as(_DBLP))
+    return out, arrs, [f]   # the last: the buffer the struct points into
+
+
+def _place_result(out, arrs, total):
+    arrs["total"] = total
+    arrs["kernel_ms"] = out.kernel_ms
+    return arrs
+
+
+def _queries(queries, M):
+    y = np.ascontiguousarray(queries, dtype=np.uint8)
+    if y.ndim == 1:
+        y = y.reshape(1, -1)
+    assert y.ndim == 2 and y.shape[1] == M
+    return y
+
+
+def placement_from_records(dataset, ab_pi, cd, queries, manycd=False, flips=None, lse=False, device=0):
+    """sr_placement: ab_pi [n_sel][count][2M+N] and cd as waic_from_records takes them, queries [Q][M] (0 absent,
+    1 present, 2 not assessed; one row may come as [M]) -> {"pos": [Q][N], the posterior probability that the query is
+    of the age of position p, "site": [Q][N], ... of the age of site n, "lpd": [Q], the log predictive density of the
+    row under a uniform prior over the positions, "total" (the number of samples), "kernel_ms"}; lse=True adds "lse"
+    [n_sel][count][Q], each sample's log of the summed likelihood.  flips [n_sel]: chains whose rows are reflected
+    first."""
+    rec = np.ascontiguousarray(ab_pi, dtype=np.int16)
+    assert rec.ndim == 3 and rec.shape[2] == 2 * dataset.M + dataset.N
+    n_sel, count = rec.shape[0], rec.shape[1]
+    r = np.ascontiguousarray(cd, dtype=np.float64)
+    assert r.shape == (n_sel, count, 2 * dataset.M if manycd else 3)
+    y = _queries(queries, dataset.M)
+    out, arrs, _keep = _place_outs(dataset.N, n_sel, count, y.shape[0], flips, lse)
+    _check(L.lib().sr_placement(ctypes.byref(dataset.c), rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)),
+                                r.ctypes.data_as(_DBLP), int(bool(manycd)), n_sel, count,
+                                y.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), y.shape[0], device,
+                                ctypes.byref(out)), "sr_placement")
+    return _place_result(out, arrs, n_sel * count)
+
+
+def placement_from_session(session, chains, queries, first=0, count=None, flips=None, lse=False):
+    """sr_session_placement: the same over a session's records still in HBM, rows [first, first + count) of chains
+    (session chain indices in selection order); shared or per-taxon rates as the session samples them."""
+    count = session_records(session) - first if count is None else count
+    ch = (ctypes.c_int32 * len(chains))(*[int(c) for c in chains])
+    y = _queries(queries, session.ds.M)
+    out, arrs, _keep = _place_outs(session.ds.N, len(chains), count, y.shape[0], flips, lse)
+    _check(L.lib().sr_session_placement(session.h, ch, len(chains), first, count,
+                                        y.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), y.shape[0],
+                                        ctypes.byref(out)), "sr_session_placement")
+    return _place_result(out, arrs, len(chains) * count)
+
+
+def placement_summary(pos, site, probs=PROBS):
+    """pos, site [Q][N] (placement_from_records) -> per query {"mean": the mean position sum_p p pos[p], "mode": the
+    first position of largest mass, "quant": int [len(probs)][Q], each the smallest p whose cumulative mass reaches
+    the probability (N - 1 where rounding keeps the total below it), "best_site": the first site of largest mass,
+    "p_best_site": its probability}.  Plain numpy, not defined to the bit."""
+    pos, site = np.atleast_2d(np.asarray(pos, np.float64)), np.atleast_2d(np.asarray(site, np.float64))
+    Q, N = pos.shape
+    cum = np.cumsum(pos, axis=1)
+    quant = np.zeros((len(probs), Q), np.int64)
+    for i, pr in enumerate(probs):
+        quant[i] = np.minimum((cum < pr).sum(axis=1), N - 1)
+    best = site.argmax(axis=1)
+    return {"mean": pos @ np.arange(N, dtype=np.float64), "mode": pos.argmax(axis=1), "quant": quant,
+            "best_site": best, "p_best_site": site[np.arange(Q), best]}
+
+
+def read_queries(path, M):
+    """A query file in the dataset's format: a header line `Q M`, then Q lines of M tokens 0, 1 or ? (not assessed);
+    a trailing * (the dataset's hard-site mark) is ignored -> uint8 [Q][M] with 2 for ?.  ValueError on anything
+    else."""
+    with open(path) as fh:
+        lines = [ln for ln in fh.read().splitlines() if ln.strip()]
+    head = lines[0].split() if lines else []
+    if len(head) != 2 or not all(t.isdigit() for t in head):
+        raise ValueError("%s: the first line must be `Q M`" % path)
+    Q, m = int(head[0]), int(head[1])
+    if m != M:
+        raise ValueError("%s: %d taxa, the dataset has %d" % (path, m, M))
+    if Q < 1 or len(lines) != 1 + Q:
+        raise ValueError("%s: %d rows announced, %d found" % (path, Q, len(lines) - 1))
+    code = {"0": 0, "1": 1, "?": 2}
+    out = np.zeros((Q, M), np.uint8)
+    for q, ln in enumerate(lines[1:]):
+        toks = ln.rstrip().rstrip("*").split()
+        if len(toks) != M:
+            raise ValueError("%s: row %d holds %d tokens, not %d" % (path, q, len(toks), M))
+        for j, t in enumerate(toks):
+            if t not in code:
+                raise ValueError("%s: row %d token %d is %r, not 0, 1 or ?" % (path, q, j, t))
+            out[q, j] = code[t]
+    return out
+
+
 # ---------------------------------------------------------------- chain agreement and modes
 # Which chains sampled the same order: per chain the exact counts of every site pair's order, the L1 distance between
 # every two chains' counts, plain and against the mirror image, and the single-linkage modes read off them
