@@ -75,3 +75,29 @@ def test_pearson_is_the_scripts_call():
         for _ in range(200 if n > 2 else 2):
             pi = [int(v) for v in rng.permutation(n)]
             assert analysis._pearson_identity(pi) == pearsonr(pi, np.arange(0, n))[0]
+
+
+def test_chain_directory_names_at_100(tmp_path):
+    """Chain ids 99, 100 and 101: the library writes Chains/chain_99, chain_100, chain_101 (chain_dir in sr_host.c:
+    two digits below 100, the plain number from 100 on; on the GPU in tests/test_gpu_e2e.py), and the Python side
+    has to look for the same names -- the file-form readers, the selection from a directory listing and the
+    distributed selection's names."""
+    names = {99: "chain_99", 100: "chain_100", 101: "chain_101"}
+    assert {k: "chain_%02d" % k for k in names} == names
+    for k, name in names.items():
+        d = tmp_path / "Chains" / name
+        d.mkdir(parents=True)
+        (d / "chain_data.csv").write_text("1 2 ,3 4 ,0 2 1 ,0.5 0.5 ,0.25 0.25 ,-%d.5\n" % k)
+        (d / "exp_data.csv").write_text("exp_loglik,exp_c,exp_d\n%s,0.5,0.25" % {99: "9.5", 100: "9.0", 101: "30.0"}[k])
+    root = str(tmp_path)
+    for k in names:
+        assert analysis._chain_lines(root, k)[0].endswith("-%d.5\n" % k)
+        assert analysis._taxa_of(root, k) == 2 and analysis._sites_of(root, k, 2) == 3
+        assert analysis.compute_exp_cd([k], 1, root=root) == (0.5 / 1000, 0.25 / 1000)
+        assert analysis.read_chain_cd(root, [k], 2)[0, 0, 2] == -(k + 0.5)
+    assert np.array_equal(analysis.read_chain_rows(root, [99, 100, 101], 3, 2)[:, 0], [[1, 2, 3, 4, 0, 2, 1]] * 3)
+    from seriation_amd import launcher
+    assert launcher.choose_chains(3, root=root) == [99, 100]   # 101 lies outside one sd of the best
+    assert launcher.choose_chains(1, root=root) == [100]
+    vals = {"chain_%02d" % k: v for k, v in [(99, 2.0), (100, 50.0), (101, 1.0)]}   # dist.select_chains' names
+    assert launcher.choose_from_values(vals, 3) == [99, 101]

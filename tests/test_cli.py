@@ -273,3 +273,23 @@ def test_gsl_rng_type_product_cli_gpu(tmp_path, rtype, code):
     if code == 0:
         fa, fb = read_dir(str(tmp_path / "o"), "chain_00"), read_dir(str(tmp_path / "p"), "chain_00")
         assert fa == fb
+
+
+@pytest.mark.gpu
+def test_product_cli_index_100(tmp_path):
+    """`mcmc 100`: the extension past the reference's two-character naming (mcmc.c:153-178 would write chain_10)
+    -- Chains/chain_100 and no other directory, the five files in it byte for byte what sr_run_to_dirs writes for
+    chain id 100 and the same seed (whose bytes tests/test_gpu_e2e.py::test_chain_ids_99_100_101 holds to the
+    oracle's; the oracle itself would take half a minute over the index form's 1000 + 1000 calls on g2s2)."""
+    import seriation_amd as sa
+    b, c = str(tmp_path / "product"), str(tmp_path / "library")
+    os.makedirs(b)
+    os.makedirs(c)
+    env = dict(os.environ, GSL_RNG_SEED="17")
+    with open(os.path.join(DS, "g2s2.txt"), "rb") as fin:
+        pb = subprocess.run([PRODUCT_CLI, "100"], cwd=b, stdin=fin, env=env, capture_output=True, timeout=900)
+    assert pb.returncode == 0, pb.stderr
+    assert os.listdir(os.path.join(b, "Chains")) == ["chain_100"]
+    sa.run_to_dirs(sa.Dataset.load(os.path.join(DS, "g2s2.txt")), [17], root=c, chain_ids=[100])
+    assert os.listdir(os.path.join(c, "Chains")) == ["chain_100"]
+    assert read_dir(b, "chain_100") == read_dir(c, "chain_100")

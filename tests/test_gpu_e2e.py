@@ -17,6 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import om_script
 import oracle_ref
 import seriation_amd as sa
 from golden.make_golden import record_digest
@@ -158,3 +159,39 @@ def test_thinning_bitexact(sweeps):
         assert np.array_equal(ri[k], o["rec_int"]), (sweeps, s)
         assert np.array_equal(rd[k].view(np.uint64), o["rec_dbl"].view(np.uint64)), (sweeps, s)
         assert [summ[k]["exp_loglik"], summ[k]["exp_c"], summ[k]["exp_d"]] == list(o["exp"])
+
+
+def test_chain_ids_99_100_101(tmp_path):
+    """The output tree at the switch from chain_NN to chain_NNN (chain_dir, sr_host.c): ids 99, 100 and 101 go to
+    Chains/chain_99, chain_100 and chain_101 and to no other spelling, each directory holds the five files with the
+    oracle CLI's bytes for its seed (the oracle run as chain 00, as above), and the file-form readers find them."""
+    ds = sa.Dataset.load(os.path.join(DS, "g2s2.txt"))
+    ids, seeds = [99, 100, 101], [21, 22, 23]
+    files = ("chain_data.csv", "exp_data.csv", "taxa.csv", "sites.csv", "hard_sites.csv")
+    (tmp_path / "gpu").mkdir()
+    summ = sa.run_to_dirs(ds, seeds, root=str(tmp_path / "gpu"), chain_ids=ids, burnin_calls=2, sample_calls=3)
+    assert [s["chain_id"] for s in summ] == ids
+    assert sorted(os.listdir(str(tmp_path / "gpu" / "Chains"))) == ["chain_100", "chain_101", "chain_99"]
+    cli = os.path.join(os.path.dirname(HERE), "oracle", "build", "mcmc_oracle")
+    for k, s in zip(ids, seeds):
+        d = tmp_path / ("cpu%d" % k)
+        (d / "Chains" / "chain_00").mkdir(parents=True)
+        with open(os.path.join(DS, "g2s2.txt"), "rb") as fin:
+            subprocess.check_call([cli, "0", "2", "3"], cwd=str(d), stdin=fin,
+                                  env=dict(os.environ, GSL_RNG_SEED=str(s)), stderr=subprocess.DEVNULL)
+        got = tmp_path / "gpu" / "Chains" / ("chain_%d" % k)
+        assert sorted(os.listdir(str(got))) == sorted(files)
+        for f in files:
+            assert (d / "Chains" / "chain_00" / f).read_bytes() == (got / f).read_bytes(), (k, f)
+    # the Python side names the directories itself ("chain_%02d" % id): it has to read that tree
+    root = str(tmp_path / "gpu")
+    rows = [om_script.read_chain_rows(os.path.join(root, "Chains", "chain_%d" % k, "chain_data.csv"), ds.N, ds.M)
+            for k in ids]
+    for j, k in enumerate(ids):
+        got = analysis.compute_exp_a([k], 1, ds.M, root=root)
+        want = om_script.exp_a([rows[j]], 1, ds.M)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), k
+    got = analysis.compute_exp_pi([100, 99], ds.N, 2, root=root)
+    assert np.array_equal(got.view(np.uint64), om_script.exp_pi([rows[1], rows[0]], ds.N, 2, ds.M).view(np.uint64))
+    chosen = launcher.choose_chains(3, root=root)
+    assert chosen and set(chosen) <= set(ids)

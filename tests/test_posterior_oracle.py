@@ -1,6 +1,9 @@
 """The posterior-summary checker (oracle/om_script.py) against the reference script's scalar loops
-transcribed literally (script.py:155-189, 230-275, 306-417), bit for bit, on small random samples.
-CPU only: the GPU kernels are compared with om_script in tests/test_gpu_posterior.py."""
+transcribed literally (script.py:155-189, 230-275, 306-417), bit for bit, on small random samples and at the edges
+the GPU matrix adds (tests/post_cases.py: chains of no rows and of one row, limits equal to the site index and one
+off it, any int16, X entries of 2, chains_selected < 0).
+CPU only: the GPU kernels are compared with om_script in tests/test_gpu_posterior.py and
+tests/test_gpu_posterior_edges.py."""
 import numpy as np
 import pytest
 
@@ -95,6 +98,32 @@ def test_om_script_matches_literal_loops(nch, ns, N, M, cs):
     rng = np.random.default_rng(nch * 100 + ns)
     rows = random_rows(rng, nch, ns, N, M)
     X = (rng.random((N, M)) < 0.4).astype(np.uint8)
+    assert same(om_script.pair_order_matrix(rows, cs, N, M), lit_po(rows, cs, N, M))
+    assert same(om_script.alive_sum(rows, cs, N, M), lit_site_taxon(rows, cs, N, M, "alive"))
+    assert same(om_script.false_alive_sum(rows, cs, N, M), lit_site_taxon(rows, cs, N, M, "false_alive"))
+    assert same(om_script.false_ones_sum(rows, cs, X, N, M), lit_site_taxon(rows, cs, N, M, "false_ones", X))
+    assert same(om_script.exp_pi(rows, N, cs, M), lit_exp_pi(rows, N, cs, M))
+    assert same(om_script.exp_a(rows, cs, M), lit_exp_a(rows, cs, M))
+
+
+# The edges the GPU matrix (tests/post_cases.py) adds: chains of no rows (0 / 1000 carried, then divided), chains
+# of one row, limits equal to the site index and one off it (with b = -1 and a > b), chains_selected < 0.
+EDGES = [("random", 2, 0, 5, 3, 8), ("random", 1, 0, 17, 17, 1), ("random", 2, 0, 4, 6, -2),
+         ("random", 7, 1, 6, 5, 3), ("limits", 1, 1, 17, 17, 4), ("limits", 3, 1, 16, 2, 2),
+         ("limits", 3, 12, 17, 16, 5), ("limits", 2, 18, 16, 17, 2), ("limits", 5, 5, 9, 7, -3),
+         ("extreme", 2, 9, 7, 8, 3)]
+
+
+@pytest.mark.parametrize("kind,nch,ns,N,M,cs", EDGES)
+def test_om_script_matches_literal_loops_at_the_edges(kind, nch, ns, N, M, cs):
+    import post_cases
+    rng = np.random.default_rng([nch, ns, N, M])
+    rec = post_cases.records(kind, N, M, nch, ns, rng)
+    rows = post_cases.chain_rows(rec)
+    assert len(rows) == nch and all(r.shape == (ns, 2 * M + N) for r in rows)
+    if kind == "limits":
+        assert post_cases.limit_events(rec, N, M).all()
+    X = post_cases.dataset_x("twos", N, M, rng)
     assert same(om_script.pair_order_matrix(rows, cs, N, M), lit_po(rows, cs, N, M))
     assert same(om_script.alive_sum(rows, cs, N, M), lit_site_taxon(rows, cs, N, M, "alive"))
     assert same(om_script.false_alive_sum(rows, cs, N, M), lit_site_taxon(rows, cs, N, M, "false_alive"))
